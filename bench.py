@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Benchmark of the denoising hot path on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W [--repeat R]
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full] [--repeat R]
   (N>1: one rank per GPU over RCCL -- under `python -m torch.distributed.run --nproc-per-node N`, as
    the driver launches it, or started plainly, in which case it re-executes itself under
    torch.distributed.run with N local ranks; --gpus must equal WORLD_SIZE)
@@ -12,15 +12,24 @@ synthetic x_T): one denoiser forward + the fused x0/clamp/update kernel, inputs 
 Weak scaling: every rank owns its own batch of 8 samples (global sample index = rank*8 + i); the
 only communication is one RCCL all-gather of the finished frames after the loop.
 
-Timing: W warmup steps, then R sweeps (default 10) of EXACTLY K steps, each sweep bracketed by a
+Timing: W warmup steps, then R sweeps (default 1) of EXACTLY K steps, each sweep bracketed by a
 barrier + torch.cuda.synchronize() on both sides and reduced with MAX over ranks; `value` and
-`ms_per_step` come from the MEDIAN sweep, `timing` carries all sweeps and the spread (R = 1
-reproduces the single-sweep protocol).  Before timing, one step of the bench configuration is
-checked against the reference's own output (tests/golden/c2_b8.npz, `verify`).
+`ms_per_step` come from the MEDIAN sweep, `timing` carries all sweeps and the spread.
 
-Prints ONE JSON line (rank 0) with the driver's contract fields plus
-  roofline     -- dominant kernel (3x3 ring conv, f16x2-split MFMA): algorithmic FLOPs / HIP-event time
-  cpu_baseline -- the CPU oracle (oracle/, torch fp32) timed on this host on a bounded sample.
+--dump-outputs DIR: after the timed sweeps, rank 0 writes what the timed path handed its caller in the
+last timed step -- the DDIM state `x` that `sampling_step` returns (all ranks' frames, gathered, for
+N > 1) -- as DIR/x.npy in float32.  Inputs (weights, x_T) are seeded, so the same arguments give the
+same inputs in every run.
+
+Prints ONE JSON line (rank 0).  A plain run does only the above; --full adds (each can be switched off
+with its --no-* option):
+  verify          -- before timing, the 50-step DDIM run of the bench configuration against the
+                     reference's own output (tests/golden/c2_b8.npz, c2_shards.npz)
+  box_calibration, rows -- this box's MFMA / copy rates; batch 1 / 32 and C3 rows (N = 1)
+  roofline        -- dominant kernel (3x3 ring conv, f16x2-split MFMA): algorithmic FLOPs / HIP-event
+                     time, with HBM traffic from two rocprofv3 PMC re-runs of this script
+  cpu_baseline    -- the CPU oracle (oracle/, torch fp32) timed on this host on a bounded sample.
+A plain run reports these fields as null.
 """
 from __future__ import annotations
 
@@ -378,14 +387,37 @@ def extra_rows(device, steps_small: int = 20):
     return rows
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, arrays: dict):
+    """--dump-outputs: each tensor as out_dir/<name>.npy in float32.  A tensor larger than DUMP_LIMIT_BYTES (over all
+    tensors) is written as a fixed sample of its flattened elements: sorted indices drawn by a generator seeded with 0."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    per = DUMP_LIMIT_BYTES // 4 // max(1, len(arrays))
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.size > per:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, per, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     global BATCH_PER_GPU
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--repeat", type=int, default=10,
-                    help="sweeps of the K timed steps (median reported; 1 = single sweep)")
+    ap.add_argument("--repeat", type=int, default=1,
+                    help="sweeps of the K timed steps (median reported; default 1 = one sweep of K steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's output as DIR/x.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the reference check, box calibration, secondary rows, roofline and CPU "
+                         "baseline (each can be switched off with its --no-* option)")
     ap.add_argument("--no-verify", action="store_true",
                     help="skip the golden-vector check of the bench configuration")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -400,6 +432,8 @@ def main():
     ap.add_argument("--conv-precision", choices=["f32", "f16x2"], default=None,
                     help="override LC_CONV_PRECISION (default f16x2)")
     args = ap.parse_args()
+    if not args.full:   # a plain run measures the headline only
+        args.no_verify = args.no_cpu_baseline = args.no_roofline = args.no_rows = args.no_traffic = True
 
     BATCH_PER_GPU = args.batch
     if args.gpus < 1 or args.repeat < 1 or args.steps < 1:
@@ -490,6 +524,8 @@ def main():
     assert torch.isfinite(frames).all()
     bad = K.range_poll(device)   # no conv layer of the timed steps ran on saturated fp16 operands
     assert not bad, f"timed steps are invalid: {bad}"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"x": all_frames if dist_on else frames})
     srt = sorted(sweeps)
     dt = srt[len(srt) // 2] if len(srt) % 2 else 0.5 * (srt[len(srt) // 2 - 1] + srt[len(srt) // 2])
 

@@ -3,7 +3,7 @@ export TMPDIR=/tmp
 T=${1:-spread}
 O=$PWD/gpurun_out/$T
 mkdir -p $O
-timeout 300 python bench.py --no-cpu-baseline --no-traffic --no-rows 2>/dev/null | tail -1 > $O/bench.json
+timeout 300 python bench.py --full --repeat 10 --no-cpu-baseline --no-traffic --no-rows 2>/dev/null | tail -1 > $O/bench.json
 timeout 600 python devtools/bench_rows.py --quick --only cond_layout_v6_32x1024,uncond_32x1024 > $O/rows.json 2>/dev/null
 python - <<PY
 import json

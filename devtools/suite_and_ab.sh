@@ -5,7 +5,7 @@ O=$PWD/gpurun_out/$T
 mkdir -p $O
 timeout 1800 python -m pytest tests -m gpu -q -p no:cacheprovider 2>&1 | grep -E "passed|failed|^FAILED|^ERROR" | tail -12 > $O/pytest.txt
 timeout 200 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1 > $O/smoke.txt
-B="timeout 300 python bench.py --no-cpu-baseline --no-traffic --no-rows"
+B="timeout 300 python bench.py --full --repeat 10 --no-cpu-baseline --no-traffic --no-rows"
 LC_FOLD_UP=0 LC_PS1X1_MIN_CO=100000 $B 2>&1 | tail -1 > $O/bench_old.json
 $B 2>&1 | tail -1 > $O/bench_new.json
 LC_FOLD_UP=0 $B 2>&1 | tail -1 > $O/bench_fold0.json

@@ -851,6 +851,35 @@ def sec_boxes():
          count=int(out.sum()))
 
 
+def sec_roipool_faces():
+    """points_in_boxes_cpu of the REFERENCE C++ (MARGIN 1e-2) on points pushed onto the box faces (+- a few ulps /
+    +- the two margins, in the box frame): inputs and flags of tests/test_oracle_vs_golden.py::
+    test_roipool_inside_test_vs_reference_cpp."""
+    sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
+    from oracle import build_c
+
+    build_c.build_ref()
+    ref = build_c.load_ref()
+    rng = np.random.default_rng(17)
+    pts = synth_points(1500, 11)[:, :3].copy()
+    bx = synth_boxes(9, pts, 12).astype(np.float32)
+    extra = []
+    for b in bx:
+        cx, cy, cz, dx, dy, dz, rz = (float(v) for v in b)
+        c, s_ = np.cos(rz), np.sin(rz)
+        for _ in range(60):
+            lx = rng.choice([-1, 1]) * (dx / 2 + rng.choice([0.0, 1e-2, 1e-5, -1e-6, 1e-6, 1.0001e-2, 0.9999e-2]))
+            ly = rng.uniform(-dy / 2, dy / 2)
+            if rng.random() < 0.5:
+                lx, ly = rng.uniform(-dx / 2, dx / 2), rng.choice([-1, 1]) * (dy / 2 + rng.choice([0.0, 1e-2, -1e-6, 1.0001e-2]))
+            z = cz + rng.choice([-1, 1]) * dz / 2 * rng.choice([1.0, 0.999999, 1.000001, 0.5])
+            extra.append([cx + lx * c - ly * s_, cy + lx * s_ + ly * c, z])
+    pts = np.concatenate([pts, np.asarray(extra, np.float32)], 0).astype(np.float32)
+    out = torch.zeros(len(bx), len(pts), dtype=torch.int32)
+    ref.points_in_boxes_cpu(torch.from_numpy(bx.copy()), torch.from_numpy(pts.copy()), out)
+    save("roipool_faces", pts=pts, boxes=bx, flags_packed=np.packbits(out.numpy().astype(np.uint8), axis=1))
+
+
 def sec_layout_cond():
     """convert_boxes_to_2d (dataset/transforms_3d/common.py:99-181) on seeded float32 boxes."""
     cm = R.ref("dataset.transforms_3d.common")

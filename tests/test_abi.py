@@ -246,7 +246,7 @@ def test_producer_stats_bookkeeping():
 
 
 def test_bench_line_contract():
-    """The committed bench line (profiles/, produced by `python bench.py` on an MI355X) carries every
+    """The committed bench line (profiles/, produced by `python bench.py --full` on an MI355X) carries every
     field of the driver's contract, the roofline and the CPU baseline objects."""
     import glob
     import json

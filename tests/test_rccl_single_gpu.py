@@ -10,6 +10,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 import torch
 
@@ -35,7 +36,7 @@ def test_bench_takes_the_rccl_path_with_one_rank():
     assert torch.cuda.is_available()
     env = _env(LC_BENCH_FORCE_DIST=1, MASTER_ADDR="127.0.0.1", MASTER_PORT=_free_port())
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "2",
-                        "--repeat", "1", "--no-cpu-baseline", "--no-traffic", "--no-rows"],
+                        "--repeat", "1", "--full", "--no-cpu-baseline", "--no-traffic", "--no-rows"],
                        env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     line = [l for l in p.stdout.splitlines() if l.startswith("{")][-1]
@@ -45,6 +46,22 @@ def test_bench_takes_the_rccl_path_with_one_rank():
     assert d["verify"]["ok"] is True                     # the 50-step check against the reference fixture ran inside it
     assert d["verify"]["ranks_verified"] == 1 and d["verify"]["per_rank"][0]["samples"] == [0, 7]
     assert d["config"].get("collectives") == "rccl: barrier + all_reduce(MAX) + all_gather of the frames executed"
+
+
+def test_plain_bench_run_times_k_steps_and_dumps_its_output(tmp_path):
+    """bench.py without --full: one sweep of exactly --steps timed steps, no reference check / rows / roofline / CPU
+    baseline, and --dump-outputs writes the DDIM state the last timed step returned."""
+    assert torch.cuda.is_available()
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2",
+                        "--dump-outputs", str(tmp_path)], env=_env(), cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-2000:]
+    d = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
+    assert d["steps"] == 3 and d["timing"]["repeat"] == 1 and len(d["timing"]["sweep_ms_per_step"]) == 1
+    assert abs(d["value"] - 1000.0 / d["ms_per_step"]) / d["value"] < 1e-3
+    for k in ("verify", "roofline", "cpu_baseline", "box_calibration", "rows"):
+        assert d[k] is None, k
+    x = np.load(tmp_path / "x.npy")
+    assert x.dtype == np.float32 and x.shape == (8, 2, 32, 1024) and np.isfinite(x).all()
 
 
 def test_bench_verifies_the_shard_of_any_rank():
