@@ -379,6 +379,18 @@ int lc_attention_f16x2_fwd(const lc_cm_operand* q, const lc_cm_operand* q_pos,
                            int64_t o_bs, int64_t o_hs, int64_t o_cs, int B, int heads, int Lq,
                            int Lk0, int Lk1, int dqk, int dpos, int dv, float scale,
                            lc_stream_t s);
+/* MeanFlow generator (MFEfficientUNet, lidargen/models/unets/efficient_mf_unet.py; csrc/flow.hip).
+ * lc_qk_norm_cm_fwd: in place, per (sample b, head h, token t) of the channel-major q and k operands -- the q / k
+ *   channel slices of the qkv projection's [B, 3C, L] output -- the d channels h*d .. h*d+d-1 (channel stride q_cs / k_cs,
+ *   unit token stride, sample stride q_bs / k_bs) become v / max(||v||_2, 1e-12) * sqrt(d) * g, g = g_q[0] / g_k[0]
+ *   (device pointers: timm Attention's q_norm / k_norm RMSNorm gains, read on the device).  d <= 64 and
+ *   B * heads <= 65535 (LC_EUNSUP), every size positive (LC_EINVAL); checked before any launch.
+ * lc_flow_step_fwd: out[b] = z[b] - dt[b] * u[b] over n elements per sample (batch strides z_bs, u_bs, out_bs; dt a
+ *   device float [B]); out == z is allowed.  The product and the difference are rounded separately, as torch does. */
+int lc_qk_norm_cm_fwd(float* q, int64_t q_bs, int64_t q_cs, float* k, int64_t k_bs, int64_t k_cs, const float* g_q,
+                      const float* g_k, int B, int heads, int d, int L, lc_stream_t s);
+int lc_flow_step_fwd(const float* z, int64_t z_bs, const float* u, int64_t u_bs, const float* dt, float* out,
+                     int64_t out_bs, int B, int64_t n, lc_stream_t s);
 /* Keys and values in UNIT FORM (round 6; csrc/attention_units.hip): the fp16 hi / lo split of lc_attention_f16x2_fwd
  * made once per step (or once per condition, for the step-invariant positional channels and the layout keys of
  * ObjectAwareCrossAttention, layout_unet_v1.py:431-476) instead of once per query block inside the attention kernel.

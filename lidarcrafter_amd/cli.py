@@ -9,6 +9,9 @@ sampler tools/evaluation/sample_and_save_cond.py): `--cfg --ckpt --device --mode
 Without --ckpt (no checkpoints ship with the reference, README.md:62) the weights are the seeded
 random initialisation used by the tests.  Layout-conditioned configs take a synthetic layout batch
 (lidarcrafter_amd.testing.synth_layout_batch) unless --batch_pt points to a saved batch dict.
+`--cfg meanflow-nusc` samples the MeanFlow generator (inference.setup_model_flow's model) in `--flow_steps` network
+calls (default 1: the reference's one-step `z - model(z, 1, 0)`); `--mode` / `--sampling_steps` do not apply to it, and
+it runs on rank 0 alone (the data-parallel helper drives the diffusion samplers' interface).
 Output per rank-0: `<out>/samples.pt` = float32 [N,5,H,W] (metric depth, x, y, z, reflectance), the
 tensor sample_and_save_cond.py:119-124,157-159 saves per sample."""
 from __future__ import annotations
@@ -31,12 +34,13 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--batch_pt", default=None, help="torch-saved layout batch dict (cond configs)")
     ap.add_argument("--out", default="samples")
+    ap.add_argument("--flow_steps", type=int, default=1, help="network calls of a flow generator (meanflow-nusc)")
     args = ap.parse_args(argv)
 
     import torch.distributed as dist
 
     from lidarcrafter_amd import parallel
-    from lidarcrafter_amd.testing import seeded_fill, synth_layout_batch
+    from lidarcrafter_amd.testing import seeded_fill, seeded_fill_qk_gains, synth_layout_batch
     from lidargen.utils import inference
     from lidargen.utils.configs import __all__ as CONFIGS
 
@@ -56,6 +60,11 @@ def main(argv=None):
 
     cfg = CONFIGS[args.cfg]()
     cfg.resume = args.ckpt
+    if hasattr(cfg, "flow"):
+        _sample_flow(args, cfg, inference, device, rank, world, seeded_fill, seeded_fill_qk_gains)
+        if dist_on:
+            dist.destroy_process_group()
+        return
     built = inference.load_model_duffusion_training(cfg)
     ddpm, model, lidar_utils = built[:3]
     if args.ckpt is None:
@@ -87,6 +96,29 @@ def main(argv=None):
               f"{dt:.2f} s ({args.sampling_steps / dt:.1f} denoising-steps/s) -> {args.out}/samples.pt")
     if dist_on:
         dist.destroy_process_group()
+
+
+def _sample_flow(args, cfg, inference, device, rank, world, seeded_fill, seeded_fill_qk_gains):
+    """Flow generators (MeanFlow): `flow_steps` network calls on rank 0, the same samples.pt layout."""
+    if rank != 0:
+        return
+    if world > 1:
+        print(f"{args.cfg}: the flow generator samples on rank 0 only ({world} ranks launched)")
+    flow, model, lidar_utils = inference.load_model_flow_training(cfg)[:3]
+    if args.ckpt is None:
+        seeded_fill(flow, salt=100)
+        seeded_fill_qk_gains(flow, salt=100)
+    flow, lidar_utils = flow.eval().to(device), lidar_utils.to(device)
+    rng = [torch.Generator().manual_seed(args.seed + i) for i in range(args.batch_size)]
+    t0 = time.perf_counter()
+    frames = flow.sample(device, batch_size=args.batch_size, num_steps=args.flow_steps, rng=rng)
+    out = lidar_utils.postprocess(frames.clamp(-1, 1))          # [B,5,H,W] fused epilogue
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    os.makedirs(args.out, exist_ok=True)
+    torch.save(out.cpu(), os.path.join(args.out, "samples.pt"))
+    print(f"{args.cfg}: {out.shape[0]} frames, {args.flow_steps} flow step(s), {dt * 1e3:.1f} ms -> "
+          f"{args.out}/samples.pt")
 
 
 if __name__ == "__main__":

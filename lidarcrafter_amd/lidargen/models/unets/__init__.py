@@ -1,7 +1,9 @@
 """Denoiser registry: the 14 names of the reference (lidargen/models/unets/__init__.py:15-30).
-On the hot path: efficient_unet, layout_unet_v1, layout_encoder, and the foreground-object branch
-of SURVEY.md §8f-3 (point_unet, object_gen_encoder).  Everything else is OUT OF SCOPE
+On the hot path: efficient_unet, layout_unet_v1, layout_encoder, the foreground-object branch
+of SURVEY.md §8f-3 (point_unet, object_gen_encoder) and, beyond SURVEY.md §8, the MeanFlow generator
+(mf_efficient_unet).  Everything else is OUT OF SCOPE
  and resolves to a stub whose constructor says so."""
+from .efficient_mf_unet import MFEfficientUNet
 from .efficient_unet import EfficientUNet
 
 
@@ -24,7 +26,6 @@ except ImportError:  # pragma: no cover - only while the conditional path is bei
 LayoutTransformerEncoderV5 = _stub("LayoutTransformerEncoderV5", "CLIP-text box encoder variant")
 LayoutUnet = _stub("LayoutUnet", "older variant of LayoutUnetV1 (no ring conv)")
 EfficientUNetCond = _stub("EfficientUNetCond", "dict-style time-arg variant of EfficientUNet")
-MFEfficientUNet = _stub("MFEfficientUNet", "MeanFlow generator (needs timm)")
 UNet1DModel = _stub("UNet1DModel", "1-D layout generator")
 SceneGraph = _stub("SceneGraph", "scene-graph GCN of the layout generator")
 SpatialRescaler = _stub("SpatialRescaler", "LDM helper")

@@ -132,8 +132,10 @@ class ResidualBlock(nn.Module):
 class Block(nn.Module):
     def __init__(self, in_channels, out_channels, num_residual_blocks, emb_channels,
                  gn_num_groups=8, gn_eps=1e-6, attn=False, attn_num_heads=8, up=1, down=1,
-                 dropout=0.0, ring=False):
+                 dropout=0.0, ring=False, attn_cls=None):
+        """`attn_cls`: the self-attention block class (default SelfAttentionBlock; MFEfficientUNet passes its own)."""
         super().__init__()
+        attn_cls = SelfAttentionBlock if attn_cls is None else attn_cls
         self.downsample = (nn.Sequential(ops.Conv2d(in_channels, out_channels, 3, 1, 1, ring=ring),
                                          ops.Resample(down=down, ring=ring))
                            if down > 1 else nn.Identity())
@@ -143,8 +145,8 @@ class Block(nn.Module):
                 in_channels=out_channels if i != 0 or down > 1 else in_channels,
                 out_channels=out_channels, emb_channels=emb_channels,
                 gn_num_groups=gn_num_groups, gn_eps=gn_eps, dropout=dropout, ring=ring))
-        self.self_attn_block = (SelfAttentionBlock(out_channels, attn_num_heads, gn_eps,
-                                                   gn_num_groups) if attn else nn.Identity())
+        self.self_attn_block = (attn_cls(out_channels, attn_num_heads, gn_eps,
+                                         gn_num_groups) if attn else nn.Identity())
         self.upsample = (nn.Sequential(ops.Resample(up=up, ring=ring),
                                        ops.Conv2d(out_channels, out_channels, 3, 1, 1, ring=ring))
                          if up > 1 else nn.Identity())
@@ -202,6 +204,8 @@ class Block(nn.Module):
 
 
 class EfficientUNet(nn.Module):
+    _attn_cls = None        # Block's default SelfAttentionBlock (MFEfficientUNet: its timm-style attention)
+
     def __init__(self, in_channels: int, resolution, out_channels: int | None = None,
                  base_channels: int = 128, temb_channels: int | None = None,
                  channel_multiplier=(1, 2, 4, 8), num_residual_blocks=(3, 3, 3, 3),
@@ -237,7 +241,7 @@ class EfficientUNet(nn.Module):
         C = [base_channels] + [base_channels * m for m in mult]
         N = _n_tuple(num_residual_blocks, L)
         cfgs = dict(emb_channels=temb_channels, gn_num_groups=gn_num_groups, gn_eps=gn_eps,
-                    attn_num_heads=attn_num_heads, dropout=0.0, ring=ring)
+                    attn_num_heads=attn_num_heads, dropout=0.0, ring=ring, attn_cls=self._attn_cls)
         self.in_conv = ops.Conv2d(in_channels, C[0], 3, 1, 1, ring=ring)
         self.d_block1 = Block(C[0], C[1], N[0], **cfgs)
         self.d_block2 = Block(C[1], C[2], N[1], down=2, **cfgs)
@@ -319,11 +323,16 @@ class EfficientUNet(nn.Module):
         if time_features is None and AG.training_active(self, images):
             # training (tools/train/train_lidm.py): the differentiable composition of the same layers
             return AG.efficient_unet_forward(self, images, timesteps.to(images))
-        B, _, H, W = images.shape
+        B = images.shape[0]
         if time_features is None:
             if timesteps.dim() == 0:
                 timesteps = timesteps[None].repeat_interleave(B, dim=0)
             time_features = self.time_features(timesteps.to(images))
+        return self._unet(images, time_features)
+
+    def _unet(self, images: torch.Tensor, time_features):
+        """The U-Net on precomputed (temb, AdaGN rows): everything of the forward after the time embedding."""
+        B, _, H, W = images.shape
         temb, ss = time_features
         ssd = self._split_ss(ss)
         C = self._C

@@ -82,6 +82,21 @@ class ModelConfig:
 
 
 @dataclass
+class FlowConfig:
+    """MeanFlow section (option_meanflow_nusc.py:23-37)."""
+    flow_type: str = "mean"
+    channels: int = 2
+    image_size: Tuple[int, int] = (32, 1024)
+    flow_ratio: float = 0.50
+    normalizer: list = field(default_factory=lambda: ["minmax", None, None])
+    time_dist: list = field(default_factory=lambda: ["lognorm", -0.4, 1])
+    cfg_ratio: float = 0.10
+    cfg_scale: Optional[float] = None
+    cfg_unconditional: str = "u"
+    jvp_api: str = "autograd"
+
+
+@dataclass
 class ConditionModelConfig:
     architecture: str = "layout_encoder"
     params: Dict[str, Any] = field(default_factory=dict)
@@ -117,9 +132,10 @@ def _merge(base: dict, **over) -> dict:
 def make_config(cls_name: str, *, model_arch: str, model_params: dict,
                 cond_arch: Optional[str] = None, cond_params: Optional[dict] = None,
                 data: Optional[dict] = None, diffusion: Optional[dict] = None,
-                training: Optional[dict] = None):
+                training: Optional[dict] = None, flow: Optional[dict] = None):
     """Build a pydantic dataclass `cls_name` with sections data/model/[condition_model]/
-    diffusion/training (+ `resume`, read by inference.load_model_duffusion_training)."""
+    diffusion/training (+ `resume`, read by inference.load_model_duffusion_training).  A flow
+    generator (`flow` given) has a `flow` section in place of `diffusion`."""
     data, diffusion, training = data or {}, diffusion or {}, training or {}
     ann: Dict[str, Any] = {}
     ns: Dict[str, Any] = {"__annotations__": ann, "__module__": __name__}
@@ -135,7 +151,10 @@ def make_config(cls_name: str, *, model_arch: str, model_params: dict,
         add("condition_model", ConditionModelConfig,
             lambda: ConditionModelConfig(architecture=cond_arch,
                                          params=copy.deepcopy(cond_params)))
-    add("diffusion", DiffusionConfig, lambda: DiffusionConfig(**copy.deepcopy(diffusion)))
+    if flow is None:
+        add("diffusion", DiffusionConfig, lambda: DiffusionConfig(**copy.deepcopy(diffusion)))
+    else:
+        add("flow", FlowConfig, lambda: FlowConfig(**copy.deepcopy(flow)))
     add("training", TrainingConfig, lambda: TrainingConfig(**copy.deepcopy(training)))
     ann["resume"] = Optional[str]
     ns["resume"] = None
@@ -194,6 +213,12 @@ NUSC_Auto_Reg_V2_Config = _layout_cfg(
     data=dict(task="autoregressive_generation"),
     training=dict(num_steps=500_000, steps_save_model=50_000))
 
+# MeanFlow generator (option_meanflow_nusc.py): MFEfficientUNet with the unconditional UNet's params,
+# sampled by models.flows.MeanFlow (built beyond SURVEY.md §8; inference.setup_model_flow).  Its data
+# and training sections set nothing but the defaults above.
+MeanFlow_NUSC_Config = make_config("MeanFlow_NUSC_Config", model_arch="mf_efficient_unet",
+                                   model_params=UNCOND_UNET, flow={})
+
 # Registry names whose generators are OUT OF SCOPE (rows 3c, 4, 5, stale KITTI
 # config).  They resolve to config objects; building their models raises NotImplementedError.
 KITTI_Config_ = make_config("KITTI_Config_", model_arch="efficient_unet",
@@ -201,8 +226,6 @@ KITTI_Config_ = make_config("KITTI_Config_", model_arch="efficient_unet",
                             data=dict(dataset="kitti_360", resolution=(64, 1024),
                                       fov_up=3.0, fov_down=-25.0))
 NUSC_HDIT_Config = make_config("NUSC_HDIT_Config", model_arch="hdit", model_params={})
-MeanFlow_NUSC_Config = make_config("MeanFlow_NUSC_Config", model_arch="mf_efficient_unet",
-                                   model_params={})
 NUSC_Layout_Config = make_config("NUSC_Layout_Config", model_arch="unet_1d", model_params={},
                                  cond_arch="scene_graph", cond_params={},
                                  data=dict(task="layout_generation"))

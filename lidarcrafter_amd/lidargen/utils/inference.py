@@ -1,5 +1,6 @@
 """Model factory -- API mirror of the reference's lidargen/utils/inference.py
-(load_model_duffusion_training :261-344, setup_model :28-105, setup_rng :460-461).  This is the
+(load_model_duffusion_training :261-344, setup_model :28-105, setup_model_flow :107-139,
+load_model_flow_training :394-457, setup_rng :460-461).  This is the
 "plugin boundary" of the reference: tools/generate/*.py and tools/evaluation/sample_and_save_*.py
 obtain (ddpm, model, lidar_utils) here, so swapping the `lidargen` package swaps in the HIP path."""
 from __future__ import annotations
@@ -13,6 +14,7 @@ import torch.nn.functional as F
 from ..models.diffusion import (CondContinuousLayoutGaussianDiffusion1D,
                                 CondContinuousTimeGaussianDiffusion,
                                 ContinuousTimeGaussianDiffusion, DiscreteTimeGaussianDiffusion)
+from ..models.flows import __all__ as __all_flows__
 from ..models.unets import __all__ as __all_unets__
 from .configs import __all__
 from .lidar import LiDARUtility, get_linear_ray_angles
@@ -132,6 +134,50 @@ def setup_model(cfg: str, ckpt, device="cpu", ema: bool = True, show_info: bool 
               f"ddpm: {ddpm.__class__.__name__}", f'#steps:  {ckpt["global_step"]:,}',
               f"#params: {count_parameters(ddpm):,}", sep="\n")
     return ddpm, lidar_utils, cfg
+
+
+def _build_flow(cfg, model):
+    f = cfg.flow
+    return __all_flows__[f.flow_type](model=model, channels=f.channels, image_size=cfg.data.resolution,
+                                      normalizer=f.normalizer, time_dist=f.time_dist, flow_ratio=f.flow_ratio,
+                                      cfg_ratio=f.cfg_ratio, cfg_scale=f.cfg_scale, jvp_api=f.jvp_api)
+
+
+def load_model_flow_training(cfg: object):
+    """MeanFlow generator (reference inference.py:394-457): -> (flow, model, lidar_utils) or, when cfg.resume is a
+    checkpoint path, (flow, model, lidar_utils, global_step, optimizer_state, lr_scheduler_state)."""
+    model = _build_denoiser(cfg)
+    flow = _build_flow(cfg, model)
+    lidar_utils = _lidar_utils(cfg, flow)
+    ckpt_path = getattr(cfg, "resume", None)
+    if ckpt_path is None:
+        return flow, model, lidar_utils
+    ckpt = torch.load(ckpt_path, map_location="cpu")
+    flow.load_state_dict(ckpt["ema_weights"])
+    flow.eval()
+    return flow, model, lidar_utils, ckpt["global_step"], ckpt["optimizer"], ckpt["lr_scheduler"]
+
+
+def setup_model_flow(cfg: str, ckpt, device="cpu", ema: bool = True, show_info: bool = True,
+                     compile: bool = False):
+    """-> (flow, lidar_utils, cfg), what tools/generate/generate_flow.py takes (reference inference.py:107-139)."""
+    if isinstance(ckpt, (str, Path)):
+        ckpt = torch.load(ckpt, map_location="cpu")
+    cfg = __all__[cfg](**ckpt["cfg"])
+    model = _build_denoiser(cfg)
+    flow = _build_flow(cfg, model)
+    flow.load_state_dict(ckpt["ema_weights"] if ema else ckpt["weights"])
+    flow.eval().to(device)
+    # `compile` is accepted for signature parity; the generator already runs hand-written kernels.
+    lidar_utils = _lidar_utils(cfg, flow).to(device)
+    if torch.device(device).type == "cuda":
+        from lidarcrafter_amd import ops as K
+        K.prepare_model(flow)
+    if show_info:
+        print(f"resolution: {model.resolution}", f"model: {model.__class__.__name__}",
+              f"ddpm: {flow.__class__.__name__}", f'#steps:  {ckpt["global_step"]:,}',
+              f"#params: {count_parameters(flow):,}", sep="\n")
+    return flow, lidar_utils, cfg
 
 
 def setup_rng(seeds: list[int], device):

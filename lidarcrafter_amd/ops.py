@@ -900,6 +900,9 @@ def prepare_model(module: torch.nn.Module) -> int:
             if att is not None and getattr(att, "in_proj_weight", None) is not None:
                 pairs.append((d["_pk_in"], att.in_proj_weight[:, :, None, None]))
                 pairs.append((d["_pk_out"], att.out_proj.weight[:, :, None, None]))
+            elif att is not None and getattr(att, "qkv", None) is not None:   # MFEfficientUNet: timm Attention's names
+                pairs.append((d["_pk_in"], att.qkv.weight[:, :, None, None]))
+                pairs.append((d["_pk_out"], att.proj.weight[:, :, None, None]))
         for pk, w in pairs:
             if not w.is_cuda or w.dim() not in (3, 4) or w.shape[-1] not in (1, 3):
                 continue
@@ -1644,6 +1647,45 @@ def attention_cm(q, k, v, heads: int, scale: float, k2=None, v2=None, q_pos=None
                  op(k2_pos, dpos), op(v2, dv), out.data_ptr(), out.stride(0), dv * out.stride(1),
                  out.stride(1), B, heads, Lq, Lk0, Lk1, dqk, dpos, dv, float(scale), _stream()),
               "lc_attention_fwd")
+    return out
+
+
+def qk_norm_cm(q: torch.Tensor, k: torch.Tensor, heads: int, g_q: torch.Tensor, g_k: torch.Tensor) -> None:
+    """In place: every head's q and k channels (q, k: [B, heads*d, L] views with arbitrary batch / channel strides and unit
+    token stride -- the q / k slices of the qkv projection's output) become F.normalize(v, dim=head) * sqrt(d) * g, the
+    RMSNorm of timm's Attention(qk_norm=True) in MFEfficientUNet.  g_q, g_k: one-element device tensors (the gains are
+    read on the device: no host sync)."""
+    for n_, t_ in (("q", q), ("k", k), ("g_q", g_q), ("g_k", g_k)):
+        _req(t_, n_)
+    if q.dim() != 3 or q.shape != k.shape or (q.shape[2] > 1 and (q.stride(2) != 1 or k.stride(2) != 1)):
+        raise ValueError("qk_norm_cm: q and k must be [B, C, L] of one shape with unit token stride")
+    if g_q.numel() != 1 or g_k.numel() != 1:
+        raise ValueError("qk_norm_cm: the gains are one-element tensors")
+    B, Cq, L = q.shape
+    if Cq % heads:
+        raise ValueError("qk_norm_cm: channels not divisible by heads")
+    with _Timed("qk_norm", 6.0 * B * Cq * L, rd=8.0 * B * Cq * L, wr=8.0 * B * Cq * L):
+        check(lib().lc_qk_norm_cm_fwd(q.data_ptr(), q.stride(0), q.stride(1), k.data_ptr(), k.stride(0), k.stride(1),
+                                      g_q.data_ptr(), g_k.data_ptr(), B, heads, Cq // heads, L, _stream()),
+              "lc_qk_norm_cm_fwd")
+
+
+def flow_step(z: torch.Tensor, u: torch.Tensor, dt: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out = z - dt[b] * u (one MeanFlow step; z, u, out: [B, C, H, W] with contiguous samples, dt: device float [B]).
+    out may be z."""
+    zb, ub = _bs4(z, "z"), _bs4(u, "u")
+    _req(dt, "dt")
+    B, C, H, W = z.shape
+    if u.shape != z.shape or dt.dim() != 1 or dt.shape[0] != B or not dt.is_contiguous():
+        raise ValueError("flow_step: u shaped like z, dt contiguous [B]")
+    if out is None:
+        out = torch.empty((B, C, H, W), device=z.device, dtype=_F32)
+    ob = _bs4(out, "out")
+    if out.shape != z.shape:
+        raise ValueError("flow_step: out shaped like z")
+    _drop_stats(out)
+    check(lib().lc_flow_step_fwd(z.data_ptr(), zb, u.data_ptr(), ub, dt.data_ptr(), out.data_ptr(), ob, B, C * H * W,
+                                 _stream()), "lc_flow_step_fwd")
     return out
 
 

@@ -38,6 +38,21 @@ def seeded_fill(module: torch.nn.Module, salt: int = 0) -> torch.nn.Module:
     return module
 
 
+@torch.no_grad()
+def seeded_fill_qk_gains(module: torch.nn.Module, salt: int = 0) -> torch.nn.Module:
+    """Give the q / k RMSNorm gains of MFEfficientUNet (`...q_norm.g`, `...k_norm.g`) magnitudes in [1.5, 2.5] with
+    mixed signs, keyed by their state_dict name; call after `seeded_fill`.  `seeded_fill` leaves them at about +-0.1
+    (one-element parameters not named `weight`), where the attention scores are nearly flat and a wrong eps, scale or
+    normalisation axis of the q / k normalisation barely shows in the output."""
+    for key, p in module.named_parameters():
+        if not key.endswith(("q_norm.g", "k_norm.g")):
+            continue
+        u = torch.rand(p.shape, generator=_gen_for(key, salt), dtype=torch.float32)
+        sign = 1.0 if zlib.crc32(key.encode()) % 2 == 0 else -1.0
+        p.copy_((sign * (1.5 + u)).to(device=p.device, dtype=p.dtype))
+    return module
+
+
 def seeded_randn(*shape: int, seed: int) -> torch.Tensor:
     g = torch.Generator(device="cpu").manual_seed(seed)
     return torch.randn(*shape, generator=g, dtype=torch.float32)
