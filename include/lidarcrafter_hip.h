@@ -391,6 +391,41 @@ int lc_qk_norm_cm_fwd(float* q, int64_t q_bs, int64_t q_cs, float* k, int64_t k_
                       const float* g_k, int B, int heads, int d, int L, lc_stream_t s);
 int lc_flow_step_fwd(const float* z, int64_t z_bs, const float* u, int64_t u_bs, const float* dt, float* out,
                      int64_t out_bs, int B, int64_t n, lc_stream_t s);
+/* MeanFlow training (csrc/flow_jvp.hip): the tangent evaluation u, du/dt = jvp(model, (z, t, r), (v, 1, 0)) of
+ * MeanFlow.loss next to the differentiable primal, and the backward of the q / k RMSNorm.
+ * lc_groupnorm_jvp_stats: per (sample, group, chunk) fp64 partials of sum(x - p), sum((x - p)^2), sum(dx), sum((x - p) dx)
+ *   (p = the group's first element) into `partials` (lc_groupnorm_jvp_partials_elems doubles); the first two exactly as
+ *   lc_groupnorm_stats forms them.
+ * lc_groupnorm_jvp_apply_train: lc_groupnorm_apply_train's y, (mean, rstd) and partial maxima of |y| (same count), plus the
+ *   tangent dy of y along (dx, dscale, dshift) (dscale / dshift may be NULL: zero; they need scale / shift) and the partial
+ *   maxima of |dy| into damax_out (may be NULL).  gamma and beta are both given or both NULL.
+ * lc_qk_norm_cm_jvp: out of place, per (sample, head, token) of channel-major operands (as lc_qk_norm_cm_fwd):
+ *   y = sqrt(d) g x / max(||x||, 1e-12) (may be NULL) and dy = J dx, J = the Jacobian of that map (dx, dy both given or
+ *   both NULL).  y is bit-identical to lc_qk_norm_cm_fwd's in-place result.
+ * lc_qk_norm_cm_bwd: gx = J gy (J symmetric) and, when dg_partials (lc_qk_norm_cm_bwd_partials doubles) and dg (one
+ *   float) are given, dg[0] = sum gy . y / g, reduced in a fixed order (no atomics).  d <= 64, B * heads <= 65535.
+ * lc_attention_jvp_fwd: plain operands as lc_attention_train_fwd (q, dq [BH, dqk, Lq], k, dk [BH, dqk, Lk], v, dv
+ *   [BH, dv, Lk]); writes o [BH, dv, Lq], lse [BH, Lq] (the base-2 log-sum-exp lc_attention_bwd* read) and the tangent
+ *   dout [BH, dv, Lq] of o along (dq, dk, dv), in one pass over the keys (exact fp32).  dqk, dv <= 64, BH <= 65535.
+ * Every entry checks its arguments before any launch (LC_EINVAL / LC_EUNSUP). */
+int64_t lc_groupnorm_jvp_partials_elems(int B, int C, int H, int W, int G);
+int lc_groupnorm_jvp_stats(const float* x, int64_t x_bs, const float* dx, int64_t dx_bs, double* partials, int B, int C,
+                           int H, int W, int G, lc_stream_t s);
+int lc_groupnorm_jvp_apply_train(const float* x, int64_t x_bs, const float* dx, int64_t dx_bs, const double* partials,
+                                 const float* gamma, const float* beta, const float* scale, const float* shift,
+                                 const float* dscale, const float* dshift, int64_t ss_bs, float* y, int64_t y_bs,
+                                 float* dy, int64_t dy_bs, int B, int C, int H, int W, int G, float eps, int act_silu,
+                                 float* mean_rstd_out, float* amax_out, float* damax_out, lc_stream_t s);
+int lc_qk_norm_cm_jvp(const float* x, int64_t x_bs, int64_t x_cs, const float* dx, int64_t dx_bs, int64_t dx_cs,
+                      const float* g, float* y, int64_t y_bs, int64_t y_cs, float* dy, int64_t dy_bs, int64_t dy_cs,
+                      int B, int heads, int d, int L, lc_stream_t s);
+int64_t lc_qk_norm_cm_bwd_partials(int B, int heads, int L);
+int lc_qk_norm_cm_bwd(const float* x, int64_t x_bs, int64_t x_cs, const float* gy, int64_t gy_bs, int64_t gy_cs,
+                      const float* g, float* gx, int64_t gx_bs, int64_t gx_cs, double* dg_partials, float* dg, int B,
+                      int heads, int d, int L, lc_stream_t s);
+int lc_attention_jvp_fwd(const float* q, const float* k, const float* v, const float* dq, const float* dk,
+                         const float* dv, float* o, float* lse, float* dout, int BH, int Lq, int Lk, int dqk, int dv_ch,
+                         float scale, lc_stream_t s);
 /* Keys and values in UNIT FORM (round 6; csrc/attention_units.hip): the fp16 hi / lo split of lc_attention_f16x2_fwd
  * made once per step (or once per condition, for the step-invariant positional channels and the layout keys of
  * ObjectAwareCrossAttention, layout_unet_v1.py:431-476) instead of once per query block inside the attention kernel.

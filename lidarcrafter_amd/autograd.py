@@ -580,3 +580,348 @@ def layout_unet_v1_forward(m, x: torch.Tensor, cond_dict: dict) -> torch.Tensor:
     for blk in m.output_blocks:
         h = seq(blk, torch.cat([h, hs.pop()], dim=1))
     return conv(m.out[2], group_norm(m.out[0], h, act=True))
+
+
+# ------------------------------------------------------------------------------------------------
+# MeanFlow (MFEfficientUNet, lidargen/models/flows/mean_flow.py MeanFlow.loss):
+#   u, dudt = jvp(model, (z, t, r), (v, 1, 0));  loss = adaptive_l2(u - sg(v - (t - r) dudt))
+# The target is stop-gradient, so the parameter gradients flow through the primal u alone: the training graph is the plain
+# differentiable forward below, and the tangent rides next to it, computed under no_grad with nothing saved (no double
+# backward).  Linear ops take their tangent through the same kernels (conv without bias, FIR resampling, concatenation);
+# GroupNorm(+AdaGN)(+SiLU), the q / k RMSNorm and the attention core have paired kernels (csrc/flow_jvp.hip) that give the
+# primal and its tangent in one pass.  Tangent convs own their PackedConv: measuring a tangent into holder["fwd"] would
+# overwrite the range record the primal conv's weight gradient splits the saved activation with.
+
+def _jvp_holder(owner, tag: str = "") -> "K.PackedConv":
+    key = "_jvp_packed" + tag
+    h = owner.__dict__.get(key)
+    if h is None:
+        h = K.PackedConv("train.jvp")
+        owner.__dict__[key] = h
+    return h
+
+
+def conv_tangent(weight, holder, dx, dres=None, out_scale=1.0):
+    """The tangent of conv(x, W) + b [+ res] scaled by out_scale: (conv(dx, W) [+ dres]) * out_scale (no bias)."""
+    w = weight if weight.dim() == 4 else weight[:, :, :, None]
+    with torch.no_grad():
+        dx = _c4(dx)
+        if TRAIN_CONV_PRECISION == "f16x2":
+            am = _amax_of(dx) if PRODUCER_AMAX else None
+            if am is not None:
+                K.range_from_amax(am[0], holder, dx.device, am[1])
+            else:
+                K.range_from_tensor(dx, holder)
+        return K.conv2d_ring(dx, holder, w.detach(), None, res=None if dres is None else _c4(dres),
+                             out_scale=float(out_scale), precision=TRAIN_CONV_PRECISION)
+
+
+class GroupNormActJvp(GroupNormAct):
+    """(y, dy): GroupNormAct's y (same statistics, same (mean, rstd) saved for the same backward) and its tangent along
+    (dx, dscale, dshift) from lc_groupnorm_jvp_stats + lc_groupnorm_jvp_apply_train.  dy is not differentiable."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, scale, shift, G, eps, act, dx, dscale, dshift):
+        x, dx = _c4(x), _c4(dx)
+        B, C, H, W = x.shape
+        dev = x.device
+        cont = lambda t: None if t is None else t.contiguous()
+        sc, sf, dsc, dsf = cont(scale), cont(shift), cont(dscale), cont(dshift)
+        n = int(lib().lc_groupnorm_jvp_partials_elems(B, C, H, W, G))
+        part = torch.empty(n, device=dev, dtype=torch.float64)
+        mr = torch.empty((B, G, 2), device=dev, dtype=torch.float32)
+        y = torch.empty(x.shape, device=dev, dtype=torch.float32)
+        dy = torch.empty(x.shape, device=dev, dtype=torch.float32)
+        p = lambda t: None if t is None else t.data_ptr()
+        with torch.cuda.device(dev):
+            st = torch.cuda.current_stream().cuda_stream
+            check(lib().lc_groupnorm_jvp_stats(x.data_ptr(), _bs(x), dx.data_ptr(), _bs(dx), part.data_ptr(), B, C, H, W,
+                                               G, st), "lc_groupnorm_jvp_stats")
+            slots = PRODUCER_AMAX and TRAIN_CONV_PRECISION == "f16x2"
+            slot = _amax_slot(dev, B, C, H, W, G, False) if slots else None
+            dslot = _amax_slot(dev, B, C, H, W, G, False) if slots else None
+            check(lib().lc_groupnorm_jvp_apply_train(x.data_ptr(), _bs(x), dx.data_ptr(), _bs(dx), part.data_ptr(),
+                                                     p(gamma), p(beta), p(sc), p(sf), p(dsc), p(dsf), C, y.data_ptr(),
+                                                     C * H * W, dy.data_ptr(), C * H * W, B, C, H, W, G, float(eps),
+                                                     int(act), mr.data_ptr(), p(slot), p(dslot), st),
+                  "lc_groupnorm_jvp_apply_train")
+        ctx.save_for_backward(x, mr, gamma, beta, sc, sf)
+        ctx.G, ctx.act = G, act
+        ctx.amax_slot = slot
+        ctx.mark_non_differentiable(dy)
+        if dslot is not None:
+            _tag_amax(dy, dslot)
+        return y, dy
+
+    @staticmethod
+    def backward(ctx, gy, _gdy):
+        return GroupNormAct.backward(ctx, gy) + (None, None, None)
+
+
+def group_norm_jvp(module, x, dx, act=False, scale=None, shift=None, dscale=None, dshift=None):
+    gamma = getattr(module, "weight", None)
+    beta = getattr(module, "bias", None)
+    y, dy = GroupNormActJvp.apply(x, gamma, beta, scale, shift, module.num_groups, module.eps, act, dx, dscale, dshift)
+    slot = getattr(y.grad_fn, "amax_slot", None) if y.grad_fn is not None else None
+    if slot is not None:
+        _tag_amax(y, slot)
+    return y, dy
+
+
+def _qk_args(t):
+    """(pointer, batch stride, channel stride) of a [B, C, L] operand with unit token stride."""
+    if t.shape[2] > 1 and t.stride(2) != 1:
+        t = t.contiguous()
+    return t, t.stride(0), t.stride(1)
+
+
+def _qk_norm_bwd(ctx, gy):
+    x, g = ctx.saved_tensors
+    gy, gy_bs, gy_cs = _qk_args(gy.float())
+    B, C, L = x.shape
+    heads = ctx.heads
+    gx = torch.empty((B, C, L), device=x.device, dtype=torch.float32)
+    dg = part = None
+    if ctx.needs_input_grad[1]:
+        part = torch.empty(int(lib().lc_qk_norm_cm_bwd_partials(B, heads, L)), device=x.device, dtype=torch.float64)
+        dg = torch.empty(1, device=x.device, dtype=torch.float32)
+    with torch.cuda.device(x.device):
+        check(lib().lc_qk_norm_cm_bwd(x.data_ptr(), x.stride(0), x.stride(1), gy.data_ptr(), gy_bs, gy_cs, g.data_ptr(),
+                                      gx.data_ptr(), C * L, L, None if part is None else part.data_ptr(),
+                                      None if dg is None else dg.data_ptr(), B, heads, C // heads, L,
+                                      torch.cuda.current_stream().cuda_stream), "lc_qk_norm_cm_bwd")
+    return gx, (None if dg is None else dg.view_as(g))
+
+
+def _qk_norm_launch(x, g, heads, dx=None, want_y=True):
+    x, x_bs, x_cs = _qk_args(x)
+    B, C, L = x.shape
+    y = torch.empty((B, C, L), device=x.device, dtype=torch.float32) if want_y else None
+    dy = None
+    dx_bs = dx_cs = 0
+    if dx is not None:
+        dx, dx_bs, dx_cs = _qk_args(dx)
+        dy = torch.empty((B, C, L), device=x.device, dtype=torch.float32)
+    with torch.cuda.device(x.device):
+        check(lib().lc_qk_norm_cm_jvp(x.data_ptr(), x_bs, x_cs, None if dx is None else dx.data_ptr(), dx_bs, dx_cs,
+                                      g.data_ptr(), None if y is None else y.data_ptr(), C * L, L,
+                                      None if dy is None else dy.data_ptr(), C * L, L, B, heads, C // heads, L,
+                                      torch.cuda.current_stream().cuda_stream), "lc_qk_norm_cm_jvp")
+    return x, y, dy
+
+
+class QKNorm(torch.autograd.Function):
+    """y = F.normalize(x, dim=head channels) * sqrt(d) * g per (sample, head, token) of a channel-major [B, heads*d, L]
+    operand (timm Attention's q_norm / k_norm RMSNorm), out of place: the backward needs the pre-norm x.  The in-place
+    lc_qk_norm_cm_fwd stays the inference kernel; y is bit-identical to it."""
+
+    @staticmethod
+    def forward(ctx, x, g, heads):
+        x, y, _ = _qk_norm_launch(x, g, heads)
+        ctx.save_for_backward(x, g)
+        ctx.heads = heads
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        gx, dg = _qk_norm_bwd(ctx, gy)
+        return gx, dg, None
+
+
+class QKNormJvp(torch.autograd.Function):
+    """(y, dy): QKNorm's y and its tangent along dx (the gain's tangent is zero in MeanFlow's jvp); dy not differentiable."""
+
+    @staticmethod
+    def forward(ctx, x, g, heads, dx):
+        x, y, dy = _qk_norm_launch(x, g, heads, dx)
+        ctx.save_for_backward(x, g)
+        ctx.heads = heads
+        ctx.mark_non_differentiable(dy)
+        return y, dy
+
+    @staticmethod
+    def backward(ctx, gy, _gdy):
+        gx, dg = _qk_norm_bwd(ctx, gy)
+        return gx, dg, None, None
+
+
+def attention_jvp_launch(q, k, v, dq, dk, dv, scale):
+    """(o, lse, do) of lc_attention_jvp_fwd for contiguous fp32 [B, h, d, L] operands."""
+    B, h, dqk, Lq = q.shape
+    Lk, dvc = k.shape[-1], v.shape[2]
+    o = torch.empty((B, h, dvc, Lq), device=q.device, dtype=torch.float32)
+    do = torch.empty_like(o)
+    lse = torch.empty((B * h, Lq), device=q.device, dtype=torch.float32)
+    with torch.cuda.device(q.device):
+        check(lib().lc_attention_jvp_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), dq.data_ptr(), dk.data_ptr(),
+                                         dv.data_ptr(), o.data_ptr(), lse.data_ptr(), do.data_ptr(), B * h, Lq, Lk, dqk,
+                                         dvc, float(scale), torch.cuda.current_stream().cuda_stream),
+              "lc_attention_jvp_fwd")
+    return o, lse, do
+
+
+class FlashAttentionJvp(torch.autograd.Function):
+    """(o, do): the flash attention of FlashAttention and its tangent along (dq, dk, dv) in one pass over the keys
+    (lc_attention_jvp_fwd).  Saves what FlashAttention saves (q, k, v, o, lse) and runs its backward."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, dq, dk, dv, scale):
+        c = lambda t: t.contiguous().float()
+        q, k, v, dq, dk, dv = c(q), c(k), c(v), c(dq), c(dk), c(dv)
+        o, lse, do = attention_jvp_launch(q, k, v, dq, dk, dv, scale)
+        ctx.save_for_backward(q, k, v, o, lse)
+        ctx.qkv_amax = None               # (the split backward measures max |q|, |k|, |v| itself)
+        ctx.scale = float(scale)
+        ctx.mark_non_differentiable(do)
+        return o, do
+
+    @staticmethod
+    def backward(ctx, go, _gdo):
+        return FlashAttention.backward(ctx, go) + (None, None, None)
+
+
+def _dsilu(a):
+    s = torch.sigmoid(a)
+    return s * (1.0 + a * (1.0 - s))
+
+
+def _mf_time_mlp(seq, x, dx):
+    """seq = Sequential(sinusoid, Linear, SiLU, Linear) of MFEfficientUNet at x [B]: (out, tangent along dx or None)."""
+    h = seq[0](x.float())                                        # [sin(x f) | cos(x f)], no parameters
+    a1 = F.linear(h, seq[1].weight, seq[1].bias)
+    out = F.linear(F.silu(a1), seq[3].weight, seq[3].bias)
+    if dx is None:
+        return out, None
+    with torch.no_grad():
+        half = h.shape[1] // 2
+        f = torch.exp(-torch.log(torch.tensor(float(seq[0].max_period))) / (half - 1) *
+                      torch.arange(half, dtype=torch.float32)).to(h.device)
+        dh = torch.cat([h[:, half:] * f, -h[:, :half] * f], 1) * dx.float()[:, None]
+        d1 = _dsilu(a1) * F.linear(dh, seq[1].weight)
+        return out, F.linear(d1, seq[3].weight)
+
+
+def _mf_walk(m, images, t, r, dz=None, dt=None, dr=None):
+    """MFEfficientUNet's forward as a differentiable graph (dz None), or that graph plus the tangent along (dz, dt, dr)."""
+    jvp = dz is not None
+    B = images.shape[0]
+    begin_training_forward(images.device)
+    t = t[None].repeat_interleave(B, dim=0) if t.dim() == 0 else t
+    r = r[None].repeat_interleave(B, dim=0) if r.dim() == 0 else r
+    if jvp:
+        dt = (dt[None].repeat_interleave(B, dim=0) if dt.dim() == 0 else dt).to(images)
+        dr = (dr[None].repeat_interleave(B, dim=0) if dr.dim() == 0 else dr).to(images)
+    ts, dts = _mf_time_mlp(m.start_time_embedding, t.to(images), dt)
+    te, dte = _mf_time_mlp(m.end_time_embedding, r.to(images), dr)
+    temb = ts + te
+    dtemb = None
+    if jvp:
+        with torch.no_grad():
+            dtemb = dts + dte
+            silu_t = _dsilu(temb) * dtemb                     # tangent of silu(temb)
+    x, dx = images, dz
+    if m.coords_encoding is not None:
+        with torch.no_grad():
+            enc = m.coords_encoding(m.coords) if not isinstance(m.coords_encoding, torch.nn.Identity) \
+                else m.coords.float()
+        x = torch.cat([images, enc.expand(B, -1, -1, -1)], dim=1)
+        if jvp:
+            with torch.no_grad():
+                dx = torch.cat([dz.float(), torch.zeros_like(enc).expand(B, -1, -1, -1)], dim=1)
+
+    def cv(mod, x, dx, res=None, dres=None, out_scale=1.0):
+        y = conv(mod, x, res=res, out_scale=out_scale)
+        return y, (conv_tangent(mod.weight, _jvp_holder(mod), dx, dres, out_scale) if jvp else None)
+
+    def gn(mod, x, dx, act, scale=None, shift=None, dscale=None, dshift=None):
+        if not jvp:
+            return group_norm(mod, x, act=act, scale=scale, shift=shift), None
+        return group_norm_jvp(mod, x, dx, act=act, scale=scale, shift=shift, dscale=dscale, dshift=dshift)
+
+    def res_block(rb, x, dx):
+        a, da = gn(rb.norm1, x, dx, True)
+        h, dh = cv(rb.conv1, a, da)
+        lin = rb.norm2.proj[1]
+        ss = F.linear(F.silu(temb), lin.weight, lin.bias)
+        C = rb.norm2.num_channels
+        dss = None
+        if jvp:
+            with torch.no_grad():
+                dss = F.linear(silu_t, lin.weight)
+        a, da = gn(rb.norm2, h, dh, True, ss[:, :C], ss[:, C:], None if dss is None else dss[:, :C],
+                   None if dss is None else dss[:, C:])
+        if isinstance(rb.skip, torch.nn.Identity):
+            sk, dsk = x, dx
+        else:
+            sk, dsk = cv(rb.skip, x, dx)
+        return cv(rb.conv2, a, da, res=sk, dres=dsk, out_scale=rb._scale_f)
+
+    def attn_block(sa, x, dx):
+        B_, C, H, W = x.shape
+        at = sa.attn
+        heads, d = at.num_heads, at.head_dim
+        a, da = gn(sa.norm, x, dx, False)
+        w_in = at.qkv.weight[:, :, None, None]
+        qkv = conv(_LinearAsConv(at.qkv.weight, at.qkv.bias, sa, "qkv"), a).view(B_, 3 * C, H * W)
+        q, k, v = qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:]
+        hv = lambda t_: t_.reshape(B_, heads, d, H * W)
+        w_out = at.proj.weight[:, :, None, None]
+        proj = _LinearAsConv(at.proj.weight, at.proj.bias, sa, "proj")
+        if not jvp:
+            qn, kn = QKNorm.apply(q, at.q_norm.g, heads), QKNorm.apply(k, at.k_norm.g, heads)
+            o = flash_attention(hv(qn), hv(kn), hv(v), at.scale)
+            return conv(proj, o.reshape(B_, C, H, W), res=x, out_scale=sa._scale_f), None
+        dqkv = conv_tangent(w_in, _jvp_holder(sa, "qkv"), da).view(B_, 3 * C, H * W)
+        qn, dqn = QKNormJvp.apply(q, at.q_norm.g, heads, dqkv[:, :C])
+        kn, dkn = QKNormJvp.apply(k, at.k_norm.g, heads, dqkv[:, C:2 * C])
+        o, do = FlashAttentionJvp.apply(hv(qn), hv(kn), hv(v), hv(dqn), hv(dkn), hv(dqkv[:, 2 * C:]), at.scale)
+        y = conv(proj, o.reshape(B_, C, H, W), res=x, out_scale=sa._scale_f)
+        return y, conv_tangent(w_out, _jvp_holder(sa, "proj"), do.reshape(B_, C, H, W), dx, sa._scale_f)
+
+    def rs(x, dx, up):
+        y = resample(x, up)
+        if not jvp:
+            return y, None
+        with torch.no_grad():
+            return y, _carry_amax(dx, K.resample2x(_c4(dx), up=up))
+
+    def block(blk, h, dh):
+        if not isinstance(blk.downsample, torch.nn.Identity):
+            h, dh = rs(*cv(blk.downsample[0], h, dh), up=False)
+        for rb in blk.residual_blocks:
+            h, dh = res_block(rb, h, dh)
+        if not isinstance(blk.self_attn_block, torch.nn.Identity):
+            h, dh = attn_block(blk.self_attn_block, h, dh)
+        if not isinstance(blk.upsample, torch.nn.Identity):
+            h, dh = cv(blk.upsample[1], *rs(h, dh, up=True))
+        return h, dh
+
+    def cat(a, b):
+        if not jvp:
+            return torch.cat([a[0], b[0]], dim=1), None
+        with torch.no_grad():
+            dcat = torch.cat([a[1], b[1]], dim=1)
+        return torch.cat([a[0], b[0]], dim=1), dcat
+
+    h = cv(m.in_conv, x, dx)
+    h1 = block(m.d_block1, *h)
+    h2 = block(m.d_block2, *h1)
+    h3 = block(m.d_block3, *h2)
+    h4 = block(m.d_block4, *h3)
+    h = block(m.u_block4, *h4)
+    h = block(m.u_block3, *cat(h, h3))
+    h = block(m.u_block2, *cat(h, h2))
+    h = block(m.u_block1, *cat(h, h1))
+    return cv(m.out_conv, *h)
+
+
+def mf_unet_forward(m, z: torch.Tensor, t: torch.Tensor, r: torch.Tensor) -> torch.Tensor:
+    """Differentiable forward of lidargen.models.unets.MFEfficientUNet (reference efficient_mf_unet.py): EfficientUNet's
+    block walk with timm's RMSNorm'd attention (QKNorm) and the time embedding start(t) + end(r)."""
+    return _mf_walk(m, z, t, r)[0]
+
+
+def mf_unet_forward_jvp(m, z, t, r, dz, dt, dr):
+    """(u, dudt): u = mf_unet_forward(m, z, t, r) with its autograd graph, and its directional derivative along
+    (dz, dt, dr), computed next to it under no_grad (dudt carries no graph, nothing is saved for it)."""
+    return _mf_walk(m, z, t, r, dz, dt, dr)

@@ -2,8 +2,14 @@
 
 The network predicts the average velocity u(z, t, r) between times r <= t, so one network call moves a sample from
 noise (t = 1) to data (r = 0): `z - model(z, 1, 0)` (MeanFlow.sample, mean_flow.py:186-199).  Sampling runs on the HIP
-path (MFEfficientUNet, ops.flow_step); training is not built here: the MeanFlow loss differentiates through a JVP of
-the network (autograd.functional.jvp with create_graph=True), i.e. double backward through every kernel.
+path (MFEfficientUNet, ops.flow_step).  Training (`loss`, mean_flow.py:128-160 of the reference):
+
+    u, dudt = jvp(model, (z, t, r), (v, 1, 0));   loss = adaptive_l2_loss(u - sg(v - (t - r) dudt))
+
+The target is stop-gradient, so the parameter gradients flow through the primal u only: no double backward is needed.
+The reference's `create_graph=True` (jvp_api "autograd") exists only because torch.autograd.functional.jvp computes a
+JVP by the double-vjp trick; "autograd" and "funtorch" give the same loss and the same gradients, and both run
+MFEfficientUNet.forward_jvp here (the differentiable forward with its tangent computed alongside, csrc/flow_jvp.hip).
 `Normalizer`, `adaptive_l2_loss` and `sample_t_r` are the reference's host code."""
 from __future__ import annotations
 
@@ -98,9 +104,34 @@ class MeanFlow(nn.Module):
         return torch.tensor(t_np, device=device), torch.tensor(r_np, device=device)
 
     def loss(self, x, c=None):
-        raise NotImplementedError(
-            "MeanFlow.loss: training is not built -- the target needs the JVP of the network "
-            "(torch.autograd.functional.jvp(..., create_graph=True)), i.e. double backward through every HIP kernel")
+        """(loss, mse_val) of the reference's MeanFlow.loss; `c` is ignored, as there.  Draws as the reference does:
+        t, r from np.random (sample_t_r), then e from torch's global CPU generator with x's shape, copied to x's device --
+        so `np.random.seed(a); torch.manual_seed(b); flow.loss(x_gpu)` draws what the reference's `flow.loss(x_cpu)`
+        draws under the same seeds."""
+        if not x.is_cuda:
+            raise NotImplementedError("MeanFlow.loss: the JVP of the network runs on the GPU kernels only "
+                                      "(MFEfficientUNet.forward_jvp); there is no CPU path")
+        t, r = self.sample_t_r(x.shape[0], x.device)
+        e = torch.randn(x.shape, dtype=x.dtype).to(x.device)
+        loss, mse_val, _, _ = self.loss_terms(x, t, r, e)
+        return loss, mse_val
+
+    def loss_terms(self, x, t, r, e):
+        """(loss, mse_val, u, dudt) for given times t, r [B] and noise e (the seam of the tests).  The tangent direction
+        is (v, 1, 0); u carries the training graph, dudt none."""
+        if not x.is_cuda:
+            raise NotImplementedError("MeanFlow.loss: the JVP of the network runs on the GPU kernels only "
+                                      "(MFEfficientUNet.forward_jvp); there is no CPU path")
+        t, r, e = t.to(x.device).float(), r.to(x.device).float(), e.to(x.device)
+        t_, r_ = t[:, None, None, None], r[:, None, None, None]
+        z = (1 - t_) * x + t_ * e
+        v = e - x
+        u, dudt = self.model.forward_jvp(z, t, r, v, torch.ones_like(t), torch.zeros_like(r))
+        u_tgt = v - (t_ - r_) * dudt
+        error = u - stopgrad(u_tgt)
+        loss = adaptive_l2_loss(error)
+        mse_val = (stopgrad(error) ** 2).mean()
+        return loss, mse_val, u, dudt
 
     def forward(self, batch):
         return self.loss(batch["x_0"], batch.get("y", None))

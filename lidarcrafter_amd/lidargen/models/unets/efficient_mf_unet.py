@@ -11,7 +11,8 @@ efficient_unet.py in two places only:
 Everything else -- ResidualBlock, Block, ring convs, FIR resampling, GroupNorm / AdaGN, Fourier coordinates, the level
 layout and every fold of the EfficientUNet hot path -- is efficient_unet.py's.  The attention runs as there (the qkv
 projection as a 1x1 conv on the GroupNorm's output, channel-major attention, `proj` + residual + 1/sqrt(2) in the conv
-epilogue) with one pass added between projection and attention: ops.qk_norm_cm (csrc/flow.hip).
+epilogue) with one pass added between projection and attention: ops.qk_norm_cm (csrc/flow.hip).  Training (MeanFlow.loss)
+runs autograd.mf_unet_forward_jvp: the differentiable forward with its tangent alongside (csrc/flow_jvp.hip).
 """
 from __future__ import annotations
 
@@ -137,12 +138,13 @@ class MFEfficientUNet(EfficientUNet):
                 condition=None, time_features=None):
         """images [B, C, H, W], start / end times [B] (or 0-d) -> [B, C_out, H, W].  `condition` is accepted and unused,
         as in the reference.  `time_features`: optional precomputed `self.time_features(t, r)` (MeanFlow.sample hoists
-        them).  Inference only: MeanFlow training needs a JVP through the network (double backward), not built."""
+        them).  In grad mode on the GPU the result is the differentiable u of autograd.mf_unet_forward (MeanFlow
+        training; its tangent comes from `forward_jvp`)."""
         if time_features is None and AG.training_active(self, images):
-            raise NotImplementedError(
-                "MFEfficientUNet: no differentiable forward (MeanFlow training needs "
-                "autograd.functional.jvp(create_graph=True) through every kernel); call it under torch.no_grad() / "
-                "torch.inference_mode()")
+            if not images.is_cuda:
+                raise NotImplementedError(
+                    "MFEfficientUNet: the jvp / training forward runs on the GPU kernels only; there is no CPU path")
+            return AG.mf_unet_forward(self, images, start_timesteps.to(images), end_timesteps.to(images))
         B = images.shape[0]
         if time_features is None:
             t, r = start_timesteps, end_timesteps
@@ -152,3 +154,17 @@ class MFEfficientUNet(EfficientUNet):
                 r = r[None].repeat_interleave(B, dim=0)
             time_features = self.time_features(t.to(images), r.to(images))
         return self._unet(images, time_features)
+
+    @torch.compiler.disable
+    @K.range_checked
+    def forward_jvp(self, images, start_timesteps, end_timesteps, d_images, d_start, d_end):
+        """(u, du) = (self(images, t, r), its directional derivative along (d_images, d_start, d_end)) -- what
+        torch.func.jvp(model, (z, t, r), (v, 1, 0)) gives MeanFlow.loss.  u carries the autograd graph of the training
+        forward when grad mode is on; du never does (the tangent runs under no_grad next to the primal: u's parameter
+        gradients are all the MeanFlow loss needs, its target being stop-gradient).  GPU only."""
+        if not images.is_cuda:
+            raise NotImplementedError(
+                "MFEfficientUNet.forward_jvp: the jvp / training forward runs on the GPU kernels only; there is no CPU path")
+        f = lambda t_: torch.as_tensor(t_, dtype=torch.float32).to(images.device)
+        return AG.mf_unet_forward_jvp(self, images, f(start_timesteps), f(end_timesteps), d_images.to(images),
+                                      f(d_start), f(d_end))
