@@ -391,6 +391,41 @@ int lc_qk_norm_cm_fwd(float* q, int64_t q_bs, int64_t q_cs, float* k, int64_t k_
                       const float* g_k, int B, int heads, int d, int L, lc_stream_t s);
 int lc_flow_step_fwd(const float* z, int64_t z_bs, const float* u, int64_t u_bs, const float* dt, float* out,
                      int64_t out_bs, int B, int64_t n, lc_stream_t s);
+/* Hourglass Diffusion Transformer (HDiT, lidargen/models/dits/hdit.py; csrc/hdit.hip).  Token grids are channel-major
+ * [B, C, h, w] with unit token stride; every size positive and every pointer non-NULL (LC_EINVAL), B (or B * heads)
+ * <= 65535 (LC_EUNSUP); all checked before any launch.
+ * lc_hdit_rmsnorm_fwd: per (sample b, token t): y[c] = x[c] * rsqrt(mean_c x^2 + eps) * f, f = 1 (mode 0),
+ *   1 + m[b * f_bs + c] (mode 1, AdaRMSNorm) or g[c] (mode 2, gain); channel strides x_cs / y_cs, L tokens.
+ *   Rows [B, C] are L = 1 with x_cs = y_cs = 1.
+ * lc_hdit_geglu_fwd: y[b, c, l] = x[b, c, l] * gelu_erf(x[b, mid + c, l]) for c < mid (x: [B, 2 mid, L] per sample).
+ * lc_hdit_qk_prep_fwd: in place on q and k ([B, heads * d, L], channel strides q_cs / k_cs, d in {32, 64}): per head,
+ *   v / max(||v||_2, 1e-6) * sqrt(exp(min(scale[head], ln 100))), then channel i < d/2 and i + d/2 rotated by
+ *   theta[head, i, t] given as cos_t / sin_t [heads, d/2, L] (the axial RoPE tables).
+ * lc_hdit_na_fwd: neighbourhood attention on an h x w grid: query (i, j) attends to rows r0 .. r0+kh-1,
+ *   r0 = clamp(i - kh/2, 0, h - kh), and columns (j - kw/2 + s) mod w, s < kw; softmax(scale * q.k) v in fp32.
+ *   kh, kw odd, kh * kw <= 81, kh <= h, kw/2 <= w, d in {32, 64} (LC_EUNSUP).  o: [B, heads * d, h * w] strides.
+ * lc_hdit_space_to_depth_fwd: out[b, (p1*P2+p2)*C + c, y, x] = in[b, c, P1*y+p1, P2*x+p2]; H % P1 == W % P2 == 0.
+ * lc_hdit_depth_to_space_fwd: out[b, c, P1*y+p1, P2*x+p2] = in[b, (p1*P2+p2)*C + c, y, x], then, when skip is given,
+ *   torch.lerp(skip, ., sigmoid(alpha[c])).  in is [B, C*P1*P2, h, w], out / skip [B, C, h*P1, w*P2] per sample.
+ * lc_hdit_tokenize_fwd: y[b, c, h, x] = sum_{ci, p} wt[c, ci, p] x[b, ci, h, P*x+p] + pe[c, h, x] (Conv2d kernel and
+ *   stride (1, P), no bias, plus the channel-major positional embedding [C, H, W/P]).
+ * lc_hdit_fourier_fwd: y[m] = [cos | sin](t[m] * 2 pi * freqs[i]), i < half; y is [M, 2 half]. */
+int lc_hdit_rmsnorm_fwd(const float* x, int64_t x_bs, int64_t x_cs, const float* f, int64_t f_bs, int mode, float* y,
+                        int64_t y_bs, int64_t y_cs, int B, int C, int L, float eps, lc_stream_t s);
+int lc_hdit_geglu_fwd(const float* x, int64_t x_bs, float* y, int64_t y_bs, int B, int mid, int L, lc_stream_t s);
+int lc_hdit_qk_prep_fwd(float* q, int64_t q_bs, int64_t q_cs, float* k, int64_t k_bs, int64_t k_cs, const float* scale,
+                        const float* cos_t, const float* sin_t, int B, int heads, int d, int L, lc_stream_t s);
+int lc_hdit_na_fwd(const lc_cm_operand* q, const lc_cm_operand* k, const lc_cm_operand* v, float* o, int64_t o_bs,
+                   int64_t o_hs, int64_t o_cs, int B, int heads, int d, int h, int w, int kh, int kw, float scale,
+                   lc_stream_t s);
+int lc_hdit_space_to_depth_fwd(const float* in, int64_t in_bs, float* out, int64_t out_bs, int B, int C, int H, int W,
+                               int P1, int P2, lc_stream_t s);
+int lc_hdit_depth_to_space_fwd(const float* in, int64_t in_bs, float* out, int64_t out_bs, const float* skip,
+                               int64_t skip_bs, const float* alpha, int B, int C, int h, int w, int P1, int P2,
+                               lc_stream_t s);
+int lc_hdit_tokenize_fwd(const float* x, int64_t x_bs, const float* wt, const float* pe, float* y, int64_t y_bs, int B,
+                         int Cin, int C, int H, int W, int P, lc_stream_t s);
+int lc_hdit_fourier_fwd(const float* t, const float* freqs, float* y, int M, int half, lc_stream_t s);
 /* MeanFlow training (csrc/flow_jvp.hip): the tangent evaluation u, du/dt = jvp(model, (z, t, r), (v, 1, 0)) of
  * MeanFlow.loss next to the differentiable primal, and the backward of the q / k RMSNorm.
  * lc_groupnorm_jvp_stats: per (sample, group, chunk) fp64 partials of sum(x - p), sum((x - p)^2), sum(dx), sum((x - p) dx)

@@ -109,6 +109,14 @@ SIGNATURES = {
     "lc_attention_units_fwd": (i32, [_op, _op, vp, vp, i64, i64, i64, i32, i32, i32, i32, i32, i32, i32, i32, f32, vp]),
     "lc_qk_norm_cm_fwd": (i32, [vp, i64, i64, vp, i64, i64, vp, vp, i32, i32, i32, i32, vp]),
     "lc_flow_step_fwd": (i32, [vp, i64, vp, i64, vp, vp, i64, i32, i64, vp]),
+    "lc_hdit_rmsnorm_fwd": (i32, [vp, i64, i64, vp, i64, i32, vp, i64, i64, i32, i32, i32, f32, vp]),
+    "lc_hdit_geglu_fwd": (i32, [vp, i64, vp, i64, i32, i32, i32, vp]),
+    "lc_hdit_qk_prep_fwd": (i32, [vp, i64, i64, vp, i64, i64, vp, vp, vp, i32, i32, i32, i32, vp]),
+    "lc_hdit_na_fwd": (i32, [_op, _op, _op, vp, i64, i64, i64, i32, i32, i32, i32, i32, i32, i32, f32, vp]),
+    "lc_hdit_space_to_depth_fwd": (i32, [vp, i64, vp, i64, i32, i32, i32, i32, i32, i32, vp]),
+    "lc_hdit_depth_to_space_fwd": (i32, [vp, i64, vp, i64, vp, i64, vp, i32, i32, i32, i32, i32, i32, vp]),
+    "lc_hdit_tokenize_fwd": (i32, [vp, i64, vp, vp, vp, i64, i32, i32, i32, i32, i32, i32, vp]),
+    "lc_hdit_fourier_fwd": (i32, [vp, vp, vp, i32, i32, vp]),
     "lc_groupnorm_jvp_partials_elems": (i64, [i32, i32, i32, i32, i32]),
     "lc_groupnorm_jvp_stats": (i32, [vp, i64, vp, i64, vp, i32, i32, i32, i32, i32, vp]),
     "lc_groupnorm_jvp_apply_train": (i32, [vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, i64, vp, i64, vp, i64,

@@ -14,6 +14,7 @@ import torch.nn.functional as F
 from ..models.diffusion import (CondContinuousLayoutGaussianDiffusion1D,
                                 CondContinuousTimeGaussianDiffusion,
                                 ContinuousTimeGaussianDiffusion, DiscreteTimeGaussianDiffusion)
+from ..models.dits import __all__ as __all_dits__
 from ..models.flows import __all__ as __all_flows__
 from ..models.unets import __all__ as __all_unets__
 from .configs import __all__
@@ -33,10 +34,10 @@ def _in_channels(cfg) -> int:
 
 def _build_denoiser(cfg):
     arch = cfg.model.architecture
-    if arch not in __all_unets__:
+    registry = __all_dits__ if "dit" in arch else __all_unets__      # as the reference dispatches
+    if arch not in registry:
         raise NotImplementedError(f"architecture {arch!r} is outside the hot path (SURVEY.md §2)")
-    model = __all_unets__[arch](in_channels=_in_channels(cfg), resolution=cfg.data.resolution,
-                                **cfg.model.params)
+    model = registry[arch](in_channels=_in_channels(cfg), resolution=cfg.data.resolution, **cfg.model.params)
     if "spherical" in cfg.data.projection:
         model.coords = get_linear_ray_angles(H=cfg.data.resolution[0], W=cfg.data.resolution[1],
                                              fov_up=cfg.data.fov_up, fov_down=cfg.data.fov_down)

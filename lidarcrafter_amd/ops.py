@@ -1689,6 +1689,221 @@ def flow_step(z: torch.Tensor, u: torch.Tensor, dt: torch.Tensor, out: Optional[
     return out
 
 
+
+# ------------------------------------------------------------------------------------ HDiT (csrc/hdit.hip)
+def _cm3(t: torch.Tensor, name: str) -> None:
+    _req(t, name)
+    if t.dim() != 3 or (t.shape[2] > 1 and t.stride(2) != 1):
+        raise ValueError(f"`{name}` must be [B, C, L] with unit token stride")
+
+
+def hdit_rmsnorm(x: torch.Tensor, mod: Optional[torch.Tensor] = None, gain: Optional[torch.Tensor] = None,
+                 eps: float = 1e-6, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """RMSNorm over the channels of every token of x ([B, C, h, w] with contiguous samples, or rows [M, C]):
+    x * rsqrt(mean_c x^2 + eps) times (1 + mod[b, c]) (AdaRMSNorm; mod a [B, C] view with unit channel stride), or
+    times gain[c], or neither."""
+    if mod is not None and gain is not None:
+        raise ValueError("hdit_rmsnorm: modulation or gain, not both")
+    rows = x.dim() == 2
+    x4 = x[:, :, None, None] if rows else x
+    if rows:
+        _req(x, "x")
+        if x.stride(1) != 1:
+            raise ValueError("hdit_rmsnorm: rows need unit channel stride")
+        x_bs = x.stride(0)
+    else:
+        x_bs = _bs4(x, "x")
+    B, C, H, W = x4.shape
+    L = H * W
+    if out is None:
+        out = torch.empty(x.shape, device=x.device, dtype=_F32)
+    if tuple(out.shape) != tuple(x.shape):
+        raise ValueError("hdit_rmsnorm: out shaped like x")
+    if rows:
+        _req(out, "out")
+        if out.stride(1) != 1:
+            raise ValueError("hdit_rmsnorm: rows need unit channel stride")
+        y_bs = out.stride(0)
+    else:
+        y_bs = _bs4(out, "out")
+    mode, f, f_bs = 0, None, 0
+    if mod is not None:
+        _req(mod, "mod")
+        if mod.shape != (B, C) or mod.stride(1) != 1:
+            raise ValueError("hdit_rmsnorm: mod must be [B, C] with unit channel stride")
+        mode, f, f_bs = 1, mod, mod.stride(0)
+    elif gain is not None:
+        _req(gain, "gain")
+        if gain.shape != (C,) or not gain.is_contiguous():
+            raise ValueError("hdit_rmsnorm: gain must be contiguous [C]")
+        mode, f = 2, gain
+    _drop_stats(out)
+    with _Timed("hdit_rmsnorm", 4.0 * B * C * L, rd=8.0 * B * C * L, wr=4.0 * B * C * L):
+        check(lib().lc_hdit_rmsnorm_fwd(x.data_ptr(), x_bs, L, _p(f), f_bs, mode, out.data_ptr(), y_bs, L, B, C, L,
+                                        float(eps), _stream()), "lc_hdit_rmsnorm_fwd")
+    return out
+
+
+def hdit_geglu(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x [B, 2 mid, h, w] (or rows [M, 2 mid]) -> x[:, :mid] * gelu_erf(x[:, mid:])."""
+    rows = x.dim() == 2
+    if rows:
+        _req(x, "x")
+        if not x.is_contiguous():
+            raise ValueError("hdit_geglu: rows must be contiguous")
+        x_bs, (B, C2), L = x.shape[1], x.shape, 1
+        shape = (B, C2 // 2)
+    else:
+        x_bs = _bs4(x, "x")
+        B, C2, H, W = x.shape
+        L, shape = H * W, (B, C2 // 2, H, W)
+    if C2 % 2:
+        raise ValueError("hdit_geglu: odd channel count")
+    if out is None:
+        out = torch.empty(shape, device=x.device, dtype=_F32)
+    if tuple(out.shape) != shape:
+        raise ValueError("hdit_geglu: out shape")
+    if rows:
+        _req(out, "out")
+        if not out.is_contiguous():
+            raise ValueError("hdit_geglu: rows must be contiguous")
+        y_bs = shape[1]
+    else:
+        y_bs = _bs4(out, "out")
+    _drop_stats(out)
+    with _Timed("hdit_geglu", 10.0 * B * C2 // 2 * L, rd=4.0 * B * C2 * L, wr=2.0 * B * C2 * L):
+        check(lib().lc_hdit_geglu_fwd(x.data_ptr(), x_bs, out.data_ptr(), y_bs, B, C2 // 2, L, _stream()),
+              "lc_hdit_geglu_fwd")
+    return out
+
+
+def hdit_qk_prep(q: torch.Tensor, k: torch.Tensor, heads: int, scale: torch.Tensor, cos_t: torch.Tensor,
+                 sin_t: torch.Tensor) -> None:
+    """In place on the q / k slices ([B, heads*d, L], unit token stride) of the qkv projection: normalise each head,
+    scale by sqrt(exp(min(scale[head], ln 100))) (scale: the device parameter, [heads] or [heads, 1]), then the axial
+    RoPE with the tables cos_t / sin_t [heads, d/2, L]."""
+    _cm3(q, "q"), _cm3(k, "k")
+    for n_, t_ in (("scale", scale), ("cos_t", cos_t), ("sin_t", sin_t)):
+        _req(t_, n_)
+    B, Cq, L = q.shape
+    if k.shape != q.shape or Cq % heads:
+        raise ValueError("hdit_qk_prep: q and k of one shape, channels divisible by heads")
+    d = Cq // heads
+    if scale.numel() != heads or not scale.is_contiguous():
+        raise ValueError("hdit_qk_prep: one contiguous scale per head")
+    for t_ in (cos_t, sin_t):
+        if tuple(t_.shape) != (heads, d // 2, L) or not t_.is_contiguous():
+            raise ValueError(f"hdit_qk_prep: RoPE tables must be contiguous [{heads}, {d // 2}, {L}]")
+    with _Timed("hdit_qk_prep", 12.0 * B * Cq * L, rd=8.0 * B * Cq * L + 8.0 * heads * d * L, wr=8.0 * B * Cq * L):
+        check(lib().lc_hdit_qk_prep_fwd(q.data_ptr(), q.stride(0), q.stride(1), k.data_ptr(), k.stride(0), k.stride(1),
+                                        scale.data_ptr(), cos_t.data_ptr(), sin_t.data_ptr(), B, heads, d, L,
+                                        _stream()), "lc_hdit_qk_prep_fwd")
+
+
+def hdit_na(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, h: int, w: int, kernel_size,
+            scale: float = 1.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Neighbourhood attention on an h x w token grid (q, k, v: [B, heads*d, h*w] channel-major views): the window of
+    query (i, j) is H-clamped (rows clamp(i - kh/2, 0, h - kh) + 0 .. kh-1) and W-circular (columns (j - kw/2 + s) mod w).
+    -> [B, heads*d, h*w]."""
+    kh, kw = kernel_size
+    for n_, t_ in (("q", q), ("k", k), ("v", v)):
+        _cm3(t_, n_)
+    B, Cq, L = q.shape
+    if k.shape != q.shape or v.shape != q.shape or L != h * w or Cq % heads:
+        raise ValueError("hdit_na: q, k, v of one [B, heads*d, h*w] shape")
+    d = Cq // heads
+    if out is None:
+        out = torch.empty((B, Cq, L), device=q.device, dtype=_F32)
+    _cm3(out, "out")
+    if tuple(out.shape) != (B, Cq, L):
+        raise ValueError("hdit_na: out shape")
+    n = kh * kw
+    with _Timed("hdit_na", 4.0 * B * Cq * L * n, rd=12.0 * B * Cq * L, wr=4.0 * B * Cq * L):
+        check(lib().lc_hdit_na_fwd(_cm_operand(q, d), _cm_operand(k, d), _cm_operand(v, d), out.data_ptr(),
+                                   out.stride(0), d * out.stride(1), out.stride(1), B, heads, d, h, w, kh, kw,
+                                   float(scale), _stream()), "lc_hdit_na_fwd")
+    return out
+
+
+def space_to_depth(x: torch.Tensor, p1: int, p2: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """[B, C, H, W] -> [B, p1*p2*C, H/p1, W/p2], channel (i*p2 + j)*C + c = x[c, p1*y + i, p2*x + j] (PatchMerging)."""
+    x_bs = _bs4(x, "x")
+    B, C, H, W = x.shape
+    shape = (B, C * p1 * p2, H // p1, W // p2)
+    if out is None:
+        out = torch.empty(shape, device=x.device, dtype=_F32)
+    o_bs = _bs4(out, "out")
+    if tuple(out.shape) != shape:
+        raise ValueError("space_to_depth: out shape")
+    _drop_stats(out)
+    check(lib().lc_hdit_space_to_depth_fwd(x.data_ptr(), x_bs, out.data_ptr(), o_bs, B, C, H, W, p1, p2, _stream()),
+          "lc_hdit_space_to_depth_fwd")
+    return out
+
+
+def depth_to_space(x: torch.Tensor, p1: int, p2: int, skip: Optional[torch.Tensor] = None,
+                   alpha: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The inverse of `space_to_depth`: [B, p1*p2*C, h, w] -> [B, C, p1*h, p2*w]; with `skip` (and `alpha` [C]) the
+    result is torch.lerp(skip, ., sigmoid(alpha)) (PatchExpanding)."""
+    x_bs = _bs4(x, "x")
+    B, Cx, h, w = x.shape
+    if Cx % (p1 * p2):
+        raise ValueError("depth_to_space: channels not divisible by p1 * p2")
+    C = Cx // (p1 * p2)
+    shape = (B, C, h * p1, w * p2)
+    s_bs = 0
+    if skip is not None:
+        s_bs = _bs4(skip, "skip")
+        _req(alpha, "alpha")
+        if tuple(skip.shape) != shape or alpha.shape != (C,) or not alpha.is_contiguous():
+            raise ValueError("depth_to_space: skip shaped like the output, alpha contiguous [C]")
+    if out is None:
+        out = torch.empty(shape, device=x.device, dtype=_F32)
+    o_bs = _bs4(out, "out")
+    if tuple(out.shape) != shape:
+        raise ValueError("depth_to_space: out shape")
+    _drop_stats(out)
+    check(lib().lc_hdit_depth_to_space_fwd(x.data_ptr(), x_bs, out.data_ptr(), o_bs, _p(skip), s_bs,
+                                           _p(alpha) if skip is not None else None, B, C, h, w, p1, p2, _stream()),
+          "lc_hdit_depth_to_space_fwd")
+    return out
+
+
+def hdit_tokenize(x: torch.Tensor, weight: torch.Tensor, pe: torch.Tensor,
+                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Conv2d(Cin -> C, kernel = stride = (1, P), no bias)(x) + pe: x [B, Cin, H, W], weight [C, Cin, 1, P],
+    pe contiguous [C, H, W/P] (channel-major positional embedding) -> [B, C, H, W/P]."""
+    x_bs = _bs4(x, "x")
+    _req(weight, "weight"), _req(pe, "pe")
+    B, Cin, H, W = x.shape
+    C, Ci, one, P = weight.shape
+    if Ci != Cin or one != 1 or W % P or not weight.is_contiguous() or not pe.is_contiguous() or \
+            tuple(pe.shape[-3:]) != (C, H, W // P) or pe.numel() != C * H * (W // P):
+        raise ValueError("hdit_tokenize: weight [C, Cin, 1, P], pe contiguous [C, H, W/P]")
+    shape = (B, C, H, W // P)
+    if out is None:
+        out = torch.empty(shape, device=x.device, dtype=_F32)
+    o_bs = _bs4(out, "out")
+    if tuple(out.shape) != shape:
+        raise ValueError("hdit_tokenize: out shape")
+    _drop_stats(out)
+    check(lib().lc_hdit_tokenize_fwd(x.data_ptr(), x_bs, weight.data_ptr(), pe.data_ptr(), out.data_ptr(), o_bs, B,
+                                     Cin, C, H, W, P, _stream()), "lc_hdit_tokenize_fwd")
+    return out
+
+
+def hdit_fourier(t: torch.Tensor, freqs: torch.Tensor) -> torch.Tensor:
+    """RandomFourierFeatures without its Linear: t [M], freqs [half] -> [M, 2 half] = [cos | sin](t (x) 2 pi freqs)."""
+    _req(t, "t"), _req(freqs, "freqs")
+    t = t.contiguous()
+    if t.dim() != 1 or freqs.dim() != 1 or not freqs.is_contiguous():
+        raise ValueError("hdit_fourier: t [M], freqs contiguous [half]")
+    M, half = t.shape[0], freqs.shape[0]
+    y = torch.empty((M, 2 * half), device=t.device, dtype=_F32)
+    check(lib().lc_hdit_fourier_fwd(t.data_ptr(), freqs.data_ptr(), y.data_ptr(), M, half, _stream()),
+          "lc_hdit_fourier_fwd")
+    return y
+
 # Keys / values in unit form (csrc/attention_units.hip): the fp16 hi / lo split of the attention operands made once per
 # step -- or once per CONDITION for the step-invariant parts -- instead of once per query block inside the kernel.
 # LC_ATTN_UNITS=0 keeps ObjectAwareCrossAttention on lc_attention_f16x2_fwd.

@@ -53,6 +53,32 @@ def seeded_fill_qk_gains(module: torch.nn.Module, salt: int = 0) -> torch.nn.Mod
     return module
 
 
+@torch.no_grad()
+def seeded_fill_hdit(module: torch.nn.Module, salt: int = 0, clamped_heads: bool = True) -> torch.nn.Module:
+    """The HDiT tensors `seeded_fill` leaves degenerate, keyed by their state_dict name; call after `seeded_fill`:
+      * the attention logit scales (`...residual_attn.scale`, [heads, 1]) near ln 10, the reference's init, and the first
+        head of every other block at 5.0 > ln 100, so the clamp at ln 100 matters (`clamped_heads=False`: not those);
+      * the RMSNorm gains (1-D `...scale`) at 1 + 0.1 r;
+      * the Fourier frequencies (buffer `timestep_pe.0.freqs`) a standard normal draw, as the reference's init;
+      * the positional embedding at 0.1 r (seeded_fill's fan-in scaling would leave it at ~1e-3)."""
+    for key, p in list(module.named_parameters()) + list(module.named_buffers()):
+        r = torch.randn(p.shape, generator=_gen_for(key, salt), dtype=torch.float32)
+        if key.endswith("residual_attn.scale"):
+            v = 2.302585092994046 + 0.3 * r
+            if clamped_heads and zlib.crc32(key.encode()) % 2 == 0:
+                v[0] = 5.0
+        elif key.endswith(".scale") and p.ndim == 1:
+            v = 1.0 + 0.1 * r
+        elif key.endswith("timestep_pe.0.freqs"):
+            v = r
+        elif key.endswith("spatial_pe.embedding"):
+            v = 0.1 * r
+        else:
+            continue
+        p.copy_(v.to(device=p.device, dtype=p.dtype))
+    return module
+
+
 def seeded_randn(*shape: int, seed: int) -> torch.Tensor:
     g = torch.Generator(device="cpu").manual_seed(seed)
     return torch.randn(*shape, generator=g, dtype=torch.float32)
