@@ -77,6 +77,12 @@ def build():
         build_ref()
     except Exception as e:  # the checker's optional half; report, do not hide
         print("oracle/_ref build failed:", e)
+    from oracle import build_ref_gpu  # the reference's GPU kernels (tests/test_reference_kernels.py)
+
+    try:
+        build_ref_gpu.build()
+    except Exception as e:
+        print("oracle/_ref GPU build failed:", e)
 
 
 if __name__ == "__main__":

@@ -4,14 +4,15 @@ Follows the CUDA kernel text of the reference,
 /root/reference/lidargen/ops/roiaware_pool3d/src/roiaware_pool3d_kernel.cu:
 generate_pts_mask_for_box3d :39-75, collect_inside_pts_for_box3d :78-108, roiaware_maxpool3d
 :111-157, roiaware_avgpool3d :160-190, *_backward :236-284.
-PARITY PARTLY PINNED: the CUDA kernels cannot run in the build container and the reference ships no
-vectors for them.  Pinned: the inside test `_local` (z slab, rotation into the box frame, the two
-half-extent comparisons) -- its arithmetic is the reference's check_pt_in_box3d, which the CUDA file
-(:23-36, MARGIN 1e-5) and the compiled C++ file (roiaware_pool3d.cpp:128-140, MARGIN 1e-2) share word
-for word except for the constant; tests/test_oracle_vs_golden.py::test_roipool_inside_test_vs_reference_cpp
-runs `_local(margin=1e-2)` against the compiled reference (oracle/_ref) on boundary-heavy point sets.
-UNPINNED (a restatement of CUDA text only): the voxel index arithmetic, the per-voxel slot order /
-overflow rule, max / avg pooling and their backward."""
+The inside test `_local` (z slab, rotation into the box frame, the two half-extent comparisons) is
+pinned on the compiled C++ file of the reference (roiaware_pool3d.cpp:128-140, MARGIN 1e-2; the CUDA
+file :23-36 shares it word for word except for MARGIN 1e-5):
+tests/test_oracle_vs_golden.py::test_roipool_inside_test_vs_reference_cpp runs `_local(margin=1e-2)`
+against it on boundary-heavy point sets.  The rest of this file (voxel index arithmetic, per-voxel
+slot order / overflow rule, max / avg pooling and their backward) restates CUDA text; what it
+restates is pinned where the product kernels are compared with the reference's own CUDA kernels,
+hipified and compiled for gfx950 with and without FP contraction (oracle/build_ref_gpu.py,
+tests/test_reference_kernels.py)."""
 from __future__ import annotations
 
 import numpy as np

@@ -1221,9 +1221,10 @@ def test_hip_graph_equals_eager(dev):
 def test_roiaware_pool3d_vs_restatement_voxel_index_slot_order_pooling_unpinned(dev, method):
     """Forward bit-exact vs the numpy restatement of the reference kernels (incl. a voxel that
     overflows max_pts_each_voxel), backward within fp32 atomics tolerance.  The restatement's inside test is pinned on
-    the compiled reference (tests/test_oracle_vs_golden.py::test_roipool_inside_test_vs_reference_cpp); its voxel
-    index arithmetic, slot order / overflow rule and the pooling follow the CUDA text only (nothing here can run it):
-    that half of the parity claim is UNPINNED, as the test name says."""
+    the compiled reference (tests/test_oracle_vs_golden.py::test_roipool_inside_test_vs_reference_cpp).  The voxel
+    index arithmetic, slot order / overflow rule, the pooling and the backward, which this restatement only follows
+    from the CUDA text (hence the test name), are now pinned on the reference's own CUDA kernels, hipified and
+    compiled for gfx950 with and without FP contraction (tests/test_reference_kernels.py)."""
     from lidarcrafter_amd.testing import synth_boxes
     from lidargen.ops.roiaware_pool3d.roiaware_pool3d_utils import RoIAwarePool3d
     from oracle import roipool as O
@@ -1770,7 +1771,10 @@ def test_discrete_time_sampler_golden(dev, golden):
 @pytest.mark.parametrize("B,N,M", [(2, 1000, 777), (1, 1, 5), (1, 512, 1024), (3, 300, 513)])
 def test_chamfer3d_vs_unpinned_restatement(dev, B, N, M):
     """lc_chamfer3d_fwd vs the float32 numpy restatement: distances and indices identical,
-    duplicates resolved to the first minimum; compute_pairwise_cd(_batch) on top of it."""
+    duplicates resolved to the first minimum; compute_pairwise_cd(_batch) on top of it.  The
+    restatement itself is unpinned; the kernel is pinned on the reference's own chamfer3D.cu,
+    hipified and compiled for gfx950 with and without FP contraction
+    (tests/test_reference_kernels.py::test_chamfer3d_vs_reference_kernel)."""
     import lidargen  # noqa: F401
     from lidargen.metrics import chamfer
     from oracle import metrics as OM
