@@ -426,6 +426,47 @@ int lc_hdit_depth_to_space_fwd(const float* in, int64_t in_bs, float* out, int64
 int lc_hdit_tokenize_fwd(const float* x, int64_t x_bs, const float* wt, const float* pe, float* y, int64_t y_bs, int B,
                          int Cin, int C, int H, int W, int P, lc_stream_t s);
 int lc_hdit_fourier_fwd(const float* t, const float* freqs, float* y, int M, int half, lc_stream_t s);
+/* HDiT training (csrc/hdit.hip, csrc/hdit_bwd.hip; lidarcrafter_amd/autograd_hdit.py).  Same conventions as the HDiT
+ * forward entries above: sizes positive and pointers non-NULL (LC_EINVAL), B (or B * heads) <= 65535, d in {32, 64}
+ * (LC_EUNSUP), all checked before any launch.  Every reduction runs in a fixed order without atomics (bit-reproducible).
+ * lc_hdit_na_train_fwd: lc_hdit_na_fwd (o bit-identical) that also stores lse[(b * heads + h) * h*w + t] = m + log l,
+ *   the log-sum-exp of the query's scaled logits.
+ * lc_hdit_rmsnorm_bwd: the backward of lc_hdit_rmsnorm_fwd (same x, f, mode, eps): dx (strides dx_bs / dx_cs, unit
+ *   token stride), and when df is given (mode 1 or 2, rs then required) d(mod)[b * df_bs + c] (mode 1) or d(gain)[c]
+ *   (mode 2) = sum of dy x rsqrt(mean x^2 + eps) over the tokens (and samples).  rs: scratch of B * L floats (the
+ *   per-token rsqrt, may be NULL without df).
+ * lc_hdit_geglu_bwd: dx[:, :mid] = dy gelu_erf(x[:, mid:]), dx[:, mid:] = dy x[:, :mid] gelu_erf'(x[:, mid:]).
+ * lc_hdit_qk_prep_bwd: the backward of lc_hdit_qk_prep_fwd taken out of place: q / k the RAW slices (before the
+ *   preparation), gq / gk the gradients of the prepared q / k, dq / dk the raw gradients (all [B, heads * d, L], their
+ *   own batch / channel strides, unit token stride).  part: scratch of heads * B * 2 * L doubles; dscale [heads] (NULL
+ *   skips it) = d(loss)/d(scale): (s / 2) sum(dq' . q' + dk' . k') / s with s = sqrt(exp(min(scale, ln 100))), 0 for
+ *   a head with scale > ln 100 (float compare, torch's clamp rule: the gradient passes at the clamp value itself).
+ * lc_hdit_na_bwd: the backward of lc_hdit_na_train_fwd: q, k, v, o, dout as operands, lse from the forward, dsum a
+ *   scratch of B * heads * h*w floats (rowsum(dout * o)); dq, dk, dv contiguous [B, heads * d, h*w].  dk / dv gather
+ *   over each key's inverse neighbourhood; the window limits are lc_hdit_na_fwd's.
+ * lc_hdit_lerp_bwd: the backward of lc_hdit_depth_to_space_fwd with skip: dout [B, C, h*P1, w*P2]; y the forward's
+ *   input in depth form [B, C*P1*P2, h, w]; dskip = (1 - a) dout, dy = space_to_depth(a dout) (batch strides
+ *   dskip_bs / dy_bs, samples contiguous), dalpha[c] = a (1 - a) sum dout (d2s(y) - skip), a = sigmoid(alpha[c])
+ *   (NULL skips it). */
+int lc_hdit_na_train_fwd(const lc_cm_operand* q, const lc_cm_operand* k, const lc_cm_operand* v, float* o,
+                         int64_t o_bs, int64_t o_hs, int64_t o_cs, float* lse, int B, int heads, int d, int h, int w,
+                         int kh, int kw, float scale, lc_stream_t s);
+int lc_hdit_rmsnorm_bwd(const float* x, int64_t x_bs, int64_t x_cs, const float* f, int64_t f_bs, int mode,
+                        const float* dy, int64_t dy_bs, int64_t dy_cs, float* dx, int64_t dx_bs, int64_t dx_cs,
+                        float* rs, float* df, int64_t df_bs, int B, int C, int L, float eps, lc_stream_t s);
+int lc_hdit_geglu_bwd(const float* x, int64_t x_bs, const float* dy, int64_t dy_bs, float* dx, int64_t dx_bs, int B,
+                      int mid, int L, lc_stream_t s);
+int lc_hdit_qk_prep_bwd(const float* q, int64_t q_bs, int64_t q_cs, const float* k, int64_t k_bs, int64_t k_cs,
+                        const float* gq, int64_t gq_bs, int64_t gq_cs, const float* gk, int64_t gk_bs, int64_t gk_cs,
+                        float* dq, int64_t dq_bs, int64_t dq_cs, float* dk, int64_t dk_bs, int64_t dk_cs,
+                        const float* scale, const float* cos_t, const float* sin_t, double* part, float* dscale, int B,
+                        int heads, int d, int L, lc_stream_t s);
+int lc_hdit_na_bwd(const lc_cm_operand* q, const lc_cm_operand* k, const lc_cm_operand* v, const lc_cm_operand* o,
+                   const lc_cm_operand* dout, const float* lse, float* dsum, float* dq, float* dk, float* dv, int B,
+                   int heads, int d, int h, int w, int kh, int kw, float scale, lc_stream_t s);
+int lc_hdit_lerp_bwd(const float* dout, int64_t dout_bs, const float* y, int64_t y_bs, const float* skip,
+                     int64_t skip_bs, const float* alpha, float* dskip, int64_t dskip_bs, float* dy, int64_t dy_bs,
+                     float* dalpha, int B, int C, int h, int w, int P1, int P2, lc_stream_t s);
 /* MeanFlow training (csrc/flow_jvp.hip): the tangent evaluation u, du/dt = jvp(model, (z, t, r), (v, 1, 0)) of
  * MeanFlow.loss next to the differentiable primal, and the backward of the q / k RMSNorm.
  * lc_groupnorm_jvp_stats: per (sample, group, chunk) fp64 partials of sum(x - p), sum((x - p)^2), sum(dx), sum((x - p) dx)

@@ -117,6 +117,14 @@ SIGNATURES = {
     "lc_hdit_depth_to_space_fwd": (i32, [vp, i64, vp, i64, vp, i64, vp, i32, i32, i32, i32, i32, i32, vp]),
     "lc_hdit_tokenize_fwd": (i32, [vp, i64, vp, vp, vp, i64, i32, i32, i32, i32, i32, i32, vp]),
     "lc_hdit_fourier_fwd": (i32, [vp, vp, vp, i32, i32, vp]),
+    "lc_hdit_na_train_fwd": (i32, [_op, _op, _op, vp, i64, i64, i64, vp, i32, i32, i32, i32, i32, i32, i32, f32, vp]),
+    "lc_hdit_rmsnorm_bwd": (i32, [vp, i64, i64, vp, i64, i32, vp, i64, i64, vp, i64, i64, vp, vp, i64, i32, i32, i32,
+                                  f32, vp]),
+    "lc_hdit_geglu_bwd": (i32, [vp, i64, vp, i64, vp, i64, i32, i32, i32, vp]),
+    "lc_hdit_qk_prep_bwd": (i32, [vp, i64, i64, vp, i64, i64, vp, i64, i64, vp, i64, i64, vp, i64, i64, vp, i64, i64,
+                                  vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
+    "lc_hdit_na_bwd": (i32, [_op, _op, _op, _op, _op, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, vp]),
+    "lc_hdit_lerp_bwd": (i32, [vp, i64, vp, i64, vp, i64, vp, vp, i64, vp, i64, vp, i32, i32, i32, i32, i32, i32, vp]),
     "lc_groupnorm_jvp_partials_elems": (i64, [i32, i32, i32, i32, i32]),
     "lc_groupnorm_jvp_stats": (i32, [vp, i64, vp, i64, vp, i32, i32, i32, i32, i32, vp]),
     "lc_groupnorm_jvp_apply_train": (i32, [vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, i64, vp, i64, vp, i64,

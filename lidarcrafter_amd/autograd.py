@@ -155,13 +155,15 @@ def _bs(t):
 class ConvRing(torch.autograd.Function):
     """y = (conv_ring(x, W) + b [+ res]) * out_scale (3x3: W circular / H zero padding, 1x1: plain).  The residual add
     and the 1/sqrt(2) of a block's exit run in the conv's epilogue, as in the inference forward; the backward
-    differentiates g = dy * out_scale through the conv and hands g to `res`."""
+    differentiates g = dy * out_scale through the conv and hands g to `res`.  `precision`: this call's arithmetic
+    ("f16x2" / "f32"); None = TRAIN_CONV_PRECISION."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, holder, amax=None, res=None, out_scale=1.0):
+    def forward(ctx, x, weight, bias, holder, amax=None, res=None, out_scale=1.0, precision=None):
+        prec = precision or TRAIN_CONV_PRECISION
         x = _c4(x)
         x_rec = None
-        if TRAIN_CONV_PRECISION == "f16x2":
+        if prec == "f16x2":
             if amax is not None:
                 K.range_from_amax(amax[0], holder["fwd"], x.device, amax[1])
             else:
@@ -170,9 +172,9 @@ class ConvRing(torch.autograd.Function):
             # (shared weights, two forwards feeding one loss) before this backward and re-measure the live record
             x_rec = holder["fwd"].range_snapshot(x.device)
         y = K.conv2d_ring(x, holder["fwd"], weight, bias, res=None if res is None else _c4(res),
-                          out_scale=float(out_scale), precision=TRAIN_CONV_PRECISION)
+                          out_scale=float(out_scale), precision=prec)
         ctx.save_for_backward(x, weight)
-        ctx.holder, ctx.has_bias, ctx.x_rec = holder, bias is not None, x_rec
+        ctx.holder, ctx.has_bias, ctx.x_rec, ctx.prec = holder, bias is not None, x_rec, prec
         ctx.out_scale, ctx.has_res = float(out_scale), res is not None
         return y
 
@@ -191,22 +193,26 @@ class ConvRing(torch.autograd.Function):
         dx = dw = db = None
         need_w = ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2])
         # the split weight gradient needs whole 2 x 32 pixel tiles and 16-byte aligned rows
-        w_split = (need_w and TRAIN_WGRAD_PRECISION == "f16x2" and TRAIN_CONV_PRECISION == "f16x2" and
+        prec = ctx.prec
+        w_split = (need_w and TRAIN_WGRAD_PRECISION == "f16x2" and prec == "f16x2" and
                    H % 2 == 0 and W % 32 == 0 and _bs(x) % 4 == 0 and _bs(dy) % 4 == 0 and
                    x.data_ptr() % 16 == 0 and dy.data_ptr() % 16 == 0)
-        if TRAIN_CONV_PRECISION == "f16x2" and (ctx.needs_input_grad[0] or w_split):
+        if prec == "f16x2" and (ctx.needs_input_grad[0] or w_split):
             if dy_amax is not None:                             # one measurement serves dX and dW
                 K.range_from_amax(dy_amax[0], ctx.holder["bwd"], dy.device, dy_amax[1])
             else:
                 K.range_from_tensor(dy, ctx.holder["bwd"])
         if ctx.needs_input_grad[0]:
-            if TRAIN_CONV_PRECISION == "f16x2":
+            if prec == "f16x2":
                 # the transposed, rotated kernel is packed straight from the forward weight
                 dx = K.conv2d_ring(dy, ctx.holder["bwd"], weight.detach(), None, precision="f16x2",
                                    weight_is_fwd=True, dx_of=ctx.holder["fwd"])
             else:
                 wt = weight.detach().flip(2, 3).transpose(0, 1).contiguous()       # [Ci, Co, ks, ks]
-                dx = K.conv2d_ring(dy, ctx.holder["bwd"], wt, None, precision=TRAIN_CONV_PRECISION)
+                # a fresh tensor per backward: the allocator may hand out the previous one's address with the same
+                # version 0, so the pack cache keyed on (address, version) must not be trusted for it
+                ctx.holder["bwd"]._key = None
+                dx = K.conv2d_ring(dy, ctx.holder["bwd"], wt, None, precision=prec)
         if need_w:
             dw = torch.empty_like(weight)
             db = torch.empty(Co, device=x.device, dtype=torch.float32) if ctx.has_bias else None
@@ -226,30 +232,34 @@ class ConvRing(torch.autograd.Function):
                                                      scratch.data_ptr(), dw.data_ptr(),
                                                      None if db is None else db.data_ptr(), B, Ci, Co, H,
                                                      W, ks, 0, st), "lc_conv2d_ring_wgrad")
-        return dx, dw, db, None, None, d_res, None
+        return dx, dw, db, None, None, d_res, None, None
 
 
-def conv(module, x, res=None, out_scale=1.0):
+def conv(module, x, res=None, out_scale=1.0, precision=None):
     """Differentiable call of an ops.Conv2d / PointwiseConv1d-like module (weight [Co,Ci,k,k]):
-    (conv(x) + bias [+ res]) * out_scale."""
+    (conv(x) + bias [+ res]) * out_scale.  `precision`: see ConvRing."""
     holder = module.__dict__.get("_train_packed")
     if holder is None:
         holder = {"fwd": K.PackedConv("train.fwd"), "bwd": K.PackedConv("train.bwd")}
         module.__dict__["_train_packed"] = holder
     w = module.weight if module.weight.dim() == 4 else module.weight[:, :, :, None]
-    if MULTI_WEIGHT_PACK and TRAIN_CONV_PRECISION == "f16x2" and w.requires_grad:
+    prec = precision or TRAIN_CONV_PRECISION
+    if MULTI_WEIGHT_PACK and TRAIN_CONV_PRECISION == "f16x2" and prec == "f16x2" and w.requires_grad:
         K.train_weight_plan(w.device).register(w, holder)
-    return ConvRing.apply(x, w, module.bias, holder, _amax_of(x) if PRODUCER_AMAX else None, res, out_scale)
+    return ConvRing.apply(x, w, module.bias, holder, _amax_of(x) if PRODUCER_AMAX else None, res, out_scale,
+                          precision)
 
 
 class FlashAttention(torch.autograd.Function):
     """o[b,h,c,t] = sum_s softmax_s(scale * sum_c' q[b,h,c',t] k[b,h,c',s]) v[b,h,c,s] for channel-major operands
     q [B,h,dqk,Lq], k [B,h,dqk,Lk], v [B,h,dv,Lk] (dqk, dv <= 64).  nn.MultiheadAttention of SelfAttentionBlock
     (efficient_unet.py:28-58) and ObjectAwareCrossAttention.forward (layout_unet_v1.py:489-506) with the content /
-    positional channels and the image / layout keys concatenated by the caller."""
+    positional channels and the image / layout keys concatenated by the caller.  `precision`: both passes' arithmetic
+    ("f16x2" / "f32"); None = TRAIN_ATTN_FWD_PRECISION / TRAIN_ATTN_BWD_PRECISION."""
 
     @staticmethod
-    def forward(ctx, q, k, v, scale):
+    def forward(ctx, q, k, v, scale, precision=None):
+        fwd_prec = precision or TRAIN_ATTN_FWD_PRECISION
         q, k, v = q.contiguous().float(), k.contiguous().float(), v.contiguous().float()
         B, h, dqk, Lq = q.shape
         Lk, dv = k.shape[-1], v.shape[2]
@@ -257,16 +267,17 @@ class FlashAttention(torch.autograd.Function):
         lse = torch.empty((B * h, Lq), device=q.device, dtype=torch.float32)
         # max |q|, |k|, |v| measured on the device by the forward entry; both passes derive the pre-scales of their fp16
         # operand splits from these three words (csrc/attention_pre.h): no host synchronisation, any operand magnitude
-        amax = torch.empty(3, device=q.device, dtype=torch.float32) if TRAIN_ATTN_FWD_PRECISION == "f16x2" else None
+        amax = torch.empty(3, device=q.device, dtype=torch.float32) if fwd_prec == "f16x2" else None
         with torch.cuda.device(q.device):
             check(lib().lc_attention_train_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(),
                                                B * h, Lq, Lk, dqk, dv, float(scale),
-                                               1 if TRAIN_ATTN_FWD_PRECISION == "f16x2" else 0,
+                                               1 if fwd_prec == "f16x2" else 0,
                                                None if amax is None else amax.data_ptr(),
                                                torch.cuda.current_stream().cuda_stream), "lc_attention_train_fwd")
         ctx.save_for_backward(q, k, v, o, lse)
         ctx.qkv_amax = amax
         ctx.scale = float(scale)
+        ctx.bwd_prec = precision or TRAIN_ATTN_BWD_PRECISION
         return o
 
     @staticmethod
@@ -281,14 +292,14 @@ class FlashAttention(torch.autograd.Function):
             st = torch.cuda.current_stream().cuda_stream
             args = (q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), do.data_ptr(), lse.data_ptr(),
                     scratch.data_ptr(), dq.data_ptr(), dk.data_ptr(), dvv.data_ptr(), B * h, Lq, Lk, dqk, dv, ctx.scale)
-            if TRAIN_ATTN_BWD_PRECISION == "f16x2":
+            if getattr(ctx, "bwd_prec", TRAIN_ATTN_BWD_PRECISION) == "f16x2":
                 amax = ctx.qkv_amax
                 if amax is None:           # (exact-fp32 forward + split backward: measure here, same rule)
                     amax = torch.stack([q.abs().amax(), k.abs().amax(), v.abs().amax()]).float()
                 check(lib().lc_attention_bwd_f16x2(*args, amax.data_ptr(), st), "lc_attention_bwd_f16x2")
             else:
                 check(lib().lc_attention_bwd(*args, st), "lc_attention_bwd")
-        return dq, dk, dvv, None
+        return dq, dk, dvv, None, None
 
 
 def flash_attention(q, k, v, scale):
@@ -777,7 +788,7 @@ class FlashAttentionJvp(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, go, _gdo):
-        return FlashAttention.backward(ctx, go) + (None, None, None)
+        return FlashAttention.backward(ctx, go)[:4] + (None, None, None)
 
 
 def _dsilu(a):

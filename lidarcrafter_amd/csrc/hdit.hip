@@ -14,7 +14,8 @@
 //  * lc_hdit_na_fwd: neighbourhood attention of query (i, j) of an h x w grid over the kh x kw keys with rows
 //    r0 .. r0+kh-1, r0 = clamp(i - kh/2, 0, h - kh) (clamped, not padded) and columns (j - kw/2 + s) mod w (circular):
 //    what the reference's circular W padding + natten's clamped windows + crop compute.  One lane per query, the q
-//    channels and the output accumulator in registers, an online fp32 softmax over the keys.
+//    channels and the output accumulator in registers, an online fp32 softmax over the keys.  lc_hdit_na_train_fwd is
+//    the same kernel storing the log-sum-exp per query as well (the backward is csrc/hdit_bwd.hip).
 //  * lc_hdit_space_to_depth_fwd / lc_hdit_depth_to_space_fwd: the patch permutes of PatchMerging
 //    (channel (p1*P2+p2)*C + c <- x[c, P1*y+p1, P2*x+p2]), PatchExpanding and the Detokenizer (the inverse); the
 //    depth-to-space optionally ends in torch.lerp(skip, ., sigmoid(alpha[c])) (PatchExpanding).
@@ -114,10 +115,12 @@ __global__ __launch_bounds__(256) void qk_prep_kernel(float* q, long long q_bs, 
     }
 }
 
-template <int D>
+// LSE: also store the log-sum-exp m + log(l) of every (sample, head, query) for the backward (lc_hdit_na_train_fwd);
+// o is computed by the same instructions either way
+template <int D, bool LSE>
 __global__ __launch_bounds__(256) void na_kernel(lc_cm_operand q, lc_cm_operand k, lc_cm_operand v, float* o,
-                                                 long long o_bs, long long o_hs, long long o_cs, int heads, int h,
-                                                 int w, int kh, int kw, float scale) {
+                                                 long long o_bs, long long o_hs, long long o_cs, float* lse,
+                                                 int heads, int h, int w, int kh, int kw, float scale) {
     const int L = h * w;
     const int t = blockIdx.x * 256 + threadIdx.x;
     if (t >= L) return;
@@ -157,6 +160,7 @@ __global__ __launch_bounds__(256) void na_kernel(lc_cm_operand q, lc_cm_operand 
     float* op = o + b * o_bs + hd * o_hs + t;
 #pragma unroll
     for (int c = 0; c < D; ++c) op[c * o_cs] = acc[c] * inv;
+    if (LSE) lse[(long long)bh * L + t] = m + logf(l);
 }
 
 // out[b, (p1*P2+p2)*C + c, y, x] = in[b, c, P1*y+p1, P2*x+p2]; one lane per output element
@@ -289,11 +293,30 @@ extern "C" int lc_hdit_na_fwd(const lc_cm_operand* q, const lc_cm_operand* k, co
     const int L = h * w;
     const dim3 grid((L + 255) / 256, B * heads);
     if (d == 32)
-        hipLaunchKernelGGL(na_kernel<32>, grid, dim3(256), 0, lc_s(s), *q, *k, *v, o, (long long)o_bs,
-                           (long long)o_hs, (long long)o_cs, heads, h, w, kh, kw, scale);
+        hipLaunchKernelGGL((na_kernel<32, false>), grid, dim3(256), 0, lc_s(s), *q, *k, *v, o, (long long)o_bs,
+                           (long long)o_hs, (long long)o_cs, nullptr, heads, h, w, kh, kw, scale);
     else
-        hipLaunchKernelGGL(na_kernel<64>, grid, dim3(256), 0, lc_s(s), *q, *k, *v, o, (long long)o_bs,
-                           (long long)o_hs, (long long)o_cs, heads, h, w, kh, kw, scale);
+        hipLaunchKernelGGL((na_kernel<64, false>), grid, dim3(256), 0, lc_s(s), *q, *k, *v, o, (long long)o_bs,
+                           (long long)o_hs, (long long)o_cs, nullptr, heads, h, w, kh, kw, scale);
+    return lc_launch_status();
+}
+
+extern "C" int lc_hdit_na_train_fwd(const lc_cm_operand* q, const lc_cm_operand* k, const lc_cm_operand* v, float* o,
+                                    int64_t o_bs, int64_t o_hs, int64_t o_cs, float* lse, int B, int heads, int d,
+                                    int h, int w, int kh, int kw, float scale, lc_stream_t s) {
+    if (!q || !k || !v || !o || !lse || !q->p || !k->p || !v->p || B <= 0 || heads <= 0 || h <= 0 || w <= 0 ||
+        kh <= 0 || kw <= 0)
+        return LC_EINVAL;
+    if (!(kh & 1) || !(kw & 1) || kh * kw > 81 || kh > h || kw / 2 > w) return LC_EUNSUP;
+    if ((d != 32 && d != 64) || (long long)B * heads > 65535 || (long long)h * w >= (1ll << 30)) return LC_EUNSUP;
+    const int L = h * w;
+    const dim3 grid((L + 255) / 256, B * heads);
+    if (d == 32)
+        hipLaunchKernelGGL((na_kernel<32, true>), grid, dim3(256), 0, lc_s(s), *q, *k, *v, o, (long long)o_bs,
+                           (long long)o_hs, (long long)o_cs, lse, heads, h, w, kh, kw, scale);
+    else
+        hipLaunchKernelGGL((na_kernel<64, true>), grid, dim3(256), 0, lc_s(s), *q, *k, *v, o, (long long)o_bs,
+                           (long long)o_hs, (long long)o_cs, lse, heads, h, w, kh, kw, scale);
     return lc_launch_status();
 }
 

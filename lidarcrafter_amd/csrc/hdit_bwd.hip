@@ -1,0 +1,465 @@
+// HDiT training (lidarcrafter_amd/autograd_hdit.py): the backward kernels of the operations csrc/hdit.hip adds to the
+// UNet path.  Every reduction over tokens or samples runs in a fixed order (no atomics): two runs give the same bits.
+//
+//  * lc_hdit_rmsnorm_bwd: dx of y = x r f (r = rsqrt(mean_c x^2 + eps), f = 1, 1 + m[b, c] or g[c]) per token, with r
+//    recomputed exactly as the forward computes it (fp64 sum of squares); dx = r g - x r^3 (sum_c g x) / C, g = dy f,
+//    in fp64.  d(mod)[b, c] = sum_t dy x r, d(gain)[c] = sum_{b, t} dy x r: one block per output, fp64 tree.
+//  * lc_hdit_geglu_bwd: da = dy gelu(g), dg = dy a gelu'(g), gelu'(g) = Phi(g) + g phi(g) (exact erf GELU).
+//  * lc_hdit_qk_prep_bwd: the adjoint of normalise -> scale -> RoPE per (sample, head, token, q / k): the rotation
+//    transposed, times s, then (du - u (u . du)) / ||v|| (du / 1e-6 where the norm was clamped); the per-token
+//    u . dp partials meet per head in a second launch: d(scale) = s / 2 * sum, 0 where scale > ln 100.
+//  * lc_hdit_na_bwd: neighbourhood attention backward from q, k, v, o, do and the forward's log-sum-exp.  First launch:
+//    one lane per query, D = do . o, P recomputed over the query's window, dq.  Second launch: one lane per key, dk and
+//    dv gathered over the key's inverse neighbourhood (rows i with r0(i) <= r <= r0(i) + kh - 1, columns
+//    (c + kw/2 - s) mod w for every s: a key that sits in a window twice when w < kw counts twice).  fp32 FMAs.
+//  * lc_hdit_lerp_bwd: PatchExpanding's torch.lerp(skip, d2s(y), sigmoid(alpha)) backward: d(skip) = (1 - a) dout,
+//    dy = s2d(a dout) (the depth-to-space permute transposed, in the same pass), d(alpha)[c] = a (1 - a) sum dout (z -
+//    skip) with z = d2s(y): one block per channel, fp64 tree.
+#include "common.h"
+
+namespace {
+
+// fixed-order fp64 tree over a 256-lane block; the result is valid in lane 0
+__device__ double block_sum256(double v, double* sh) {
+    sh[threadIdx.x] = v;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
+        __syncthreads();
+    }
+    return sh[0];
+}
+
+// 64 tokens x 4 channel quarters per block, as the forward: r recomputed bit for bit, then sum_c g x, then dx
+__global__ __launch_bounds__(256) void rmsnorm_bwd_kernel(const float* __restrict__ x, long long x_bs, long long x_cs,
+                                                          const float* __restrict__ f, long long f_bs, int mode,
+                                                          const float* __restrict__ dy, long long dy_bs,
+                                                          long long dy_cs, float* dx, long long dx_bs,
+                                                          long long dx_cs, float* rs, int C, int L, float eps) {
+    __shared__ double part[4][64];
+    const int lane = threadIdx.x & 63, qtr = threadIdx.x >> 6;
+    const int t = blockIdx.x * 64 + lane;
+    const int b = blockIdx.y;
+    const int cq = (C + 3) / 4;
+    const int c0 = qtr * cq, c1 = min(C, c0 + cq);
+    const bool live = t < L;
+    const float* xp = x + b * x_bs + (live ? t : 0);
+    const float* gp = dy + b * dy_bs + (live ? t : 0);
+    const float* fp = mode == 1 ? f + b * f_bs : f;
+    double ss = 0.0;
+    if (live) {
+#pragma unroll 4
+        for (int c = c0; c < c1; ++c) {
+            const double v = (double)xp[c * x_cs];
+            ss = fma(v, v, ss);
+        }
+    }
+    part[qtr][lane] = ss;
+    __syncthreads();
+    ss = ((part[0][lane] + part[1][lane]) + part[2][lane]) + part[3][lane];
+    const float r = (float)(1.0 / sqrt((double)(float)(ss / C) + (double)eps));
+    double dot = 0.0;
+    if (live) {
+#pragma unroll 4
+        for (int c = c0; c < c1; ++c) {
+            float g = gp[c * dy_cs];
+            if (mode == 1)
+                g = g * (1.0f + fp[c]);
+            else if (mode == 2)
+                g = g * fp[c];
+            dot = fma((double)g, (double)xp[c * x_cs], dot);
+        }
+    }
+    __syncthreads();
+    part[qtr][lane] = dot;
+    __syncthreads();
+    if (!live) return;
+    dot = ((part[0][lane] + part[1][lane]) + part[2][lane]) + part[3][lane];
+    const double rd = (double)r;
+    const double k = rd * rd * rd * dot / C;
+    if (qtr == 0 && rs) rs[(long long)b * L + t] = r;
+    float* op = dx + b * dx_bs + t;
+#pragma unroll 4
+    for (int c = c0; c < c1; ++c) {
+        float g = gp[c * dy_cs];
+        if (mode == 1)
+            g = g * (1.0f + fp[c]);
+        else if (mode == 2)
+            g = g * fp[c];
+        op[c * dx_cs] = (float)(rd * (double)g - (double)xp[c * x_cs] * k);
+    }
+}
+
+// d(mod)[b, c] (mode 1: blockIdx.y = b) or d(gain)[c] (mode 2: every sample): sum over tokens of dy x r
+__global__ __launch_bounds__(256) void rmsnorm_dparam_kernel(const float* __restrict__ x, long long x_bs,
+                                                             long long x_cs, const float* __restrict__ dy,
+                                                             long long dy_bs, long long dy_cs,
+                                                             const float* __restrict__ rs, float* df, long long df_bs,
+                                                             int mode, int B, int L) {
+    __shared__ double sh[256];
+    const int c = blockIdx.x;
+    const int b0 = mode == 1 ? blockIdx.y : 0, b1 = mode == 1 ? b0 + 1 : B;
+    double acc = 0.0;
+    for (int b = b0; b < b1; ++b) {
+        const float* xp = x + b * x_bs + c * x_cs;
+        const float* gp = dy + b * dy_bs + c * dy_cs;
+        const float* rp = rs + (long long)b * L;
+        for (int t = threadIdx.x; t < L; t += 256)
+            acc = fma((double)gp[t] * (double)xp[t], (double)rp[t], acc);
+    }
+    const double s = block_sum256(acc, sh);
+    if (threadIdx.x == 0) df[(mode == 1 ? blockIdx.y * df_bs : 0) + c] = (float)s;
+}
+
+__device__ __forceinline__ float gelu_erf(float g) { return 0.5f * g * (1.0f + erff(g * 0.70710678118654752f)); }
+
+__device__ __forceinline__ float dgelu_erf(float g) {
+    return 0.5f * (1.0f + erff(g * 0.70710678118654752f)) + g * 0.39894228040143268f * expf(-0.5f * g * g);
+}
+
+__global__ __launch_bounds__(256) void geglu_bwd_kernel(const float* __restrict__ x, long long x_bs,
+                                                        const float* __restrict__ dy, long long dy_bs, float* dx,
+                                                        long long dx_bs, int mid, int L) {
+    const int b = blockIdx.y;
+    const long long n = (long long)mid * L;
+    const float* xp = x + b * x_bs;
+    const float* gp = dy + b * dy_bs;
+    float* op = dx + b * dx_bs;
+    for (long long i = blockIdx.x * 256ll + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+        const float a = xp[i], g = xp[i + n], d = gp[i];
+        op[i] = d * gelu_erf(g);
+        op[i + n] = d * a * dgelu_erf(g);
+    }
+}
+
+template <int D>
+__global__ __launch_bounds__(256) void qk_prep_bwd_kernel(
+    const float* __restrict__ q, long long q_bs, long long q_cs, const float* __restrict__ k, long long k_bs,
+    long long k_cs, const float* __restrict__ gq, long long gq_bs, long long gq_cs, const float* __restrict__ gk,
+    long long gk_bs, long long gk_cs, float* dq, long long dq_bs, long long dq_cs, float* dk, long long dk_bs,
+    long long dk_cs, const float* __restrict__ scale, const float* __restrict__ cos_t,
+    const float* __restrict__ sin_t, double* part, int B, int heads, int L) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= L) return;
+    const int bh = blockIdx.y;
+    const int b = bh / heads, h = bh - b * heads;
+    const bool is_k = blockIdx.z != 0;
+    const long long cs = is_k ? k_cs : q_cs, gcs = is_k ? gk_cs : gq_cs, ocs = is_k ? dk_cs : dq_cs;
+    const float* p = (is_k ? k + b * k_bs : q + b * q_bs) + (long long)h * D * cs + t;
+    const float* gp = (is_k ? gk + b * gk_bs : gq + b * gq_bs) + (long long)h * D * gcs + t;
+    float* op = (is_k ? dk + b * dk_bs : dq + b * dq_bs) + (long long)h * D * ocs + t;
+    float v[D], g[D];
+    double ss = 0.0;
+#pragma unroll
+    for (int c = 0; c < D; ++c) {
+        v[c] = p[c * cs];
+        ss = fma((double)v[c], (double)v[c], ss);
+    }
+    const double nrm_exact = sqrt(ss);
+    const float nrm = fmaxf((float)nrm_exact, 1e-6f);
+    const float sc = sqrtf(expf(fminf(scale[h], 4.60517018598809136f)));
+    // dp = R^T dout
+    const float* ct = cos_t + (long long)h * (D / 2) * L + t;
+    const float* st = sin_t + (long long)h * (D / 2) * L + t;
+#pragma unroll
+    for (int i = 0; i < D / 2; ++i) {
+        const float c = ct[(long long)i * L], s = st[(long long)i * L];
+        const float g1 = gp[i * gcs], g2 = gp[(i + D / 2) * gcs];
+        g[i] = fmaf(g1, c, g2 * s);
+        g[i + D / 2] = fmaf(g2, c, -(g1 * s));
+    }
+    // u = v / nrm;  dL/ds partial = dp . u;  du = s dp;  dv = (du - u (u . du)) / nrm (du / nrm when clamped)
+    double pu = 0.0;
+#pragma unroll
+    for (int c = 0; c < D; ++c) pu = fma((double)g[c], (double)(v[c] / nrm), pu);
+    const bool clamped = !((float)nrm_exact > 1e-6f);
+    const double coef = clamped ? 0.0 : pu * (double)sc;              // u . du
+    const double inv = 1.0 / (double)nrm;
+#pragma unroll
+    for (int c = 0; c < D; ++c) {
+        const double u = (double)v[c] * inv;
+        op[c * ocs] = (float)(((double)sc * (double)g[c] - u * coef) * inv);
+    }
+    part[(((long long)h * B + b) * 2 + (is_k ? 1 : 0)) * L + t] = pu;
+}
+
+__global__ __launch_bounds__(256) void qk_scale_grad_kernel(const double* __restrict__ part,
+                                                            const float* __restrict__ scale, float* dscale, int B,
+                                                            int L) {
+    __shared__ double sh[256];
+    const int h = blockIdx.x;
+    const long long n = (long long)B * 2 * L;
+    const double* p = part + (long long)h * n;
+    double acc = 0.0;
+    for (long long i = threadIdx.x; i < n; i += 256) acc += p[i];
+    const double s = block_sum256(acc, sh);
+    if (threadIdx.x == 0) {
+        // torch: clamp(max = ln 100) passes the gradient where scale <= ln 100 (compared in float)
+        const float sv = scale[h];
+        const float sc = sqrtf(expf(fminf(sv, 4.60517018598809136f)));
+        dscale[h] = sv <= 4.60517018598809136f ? (float)(s * (double)sc * 0.5) : 0.0f;
+    }
+}
+
+__device__ __forceinline__ int na_r0(int i, int h, int kh) {
+    int r0 = i - kh / 2;
+    return r0 < 0 ? 0 : (r0 > h - kh ? h - kh : r0);
+}
+
+__device__ __forceinline__ int wrap(int c, int w) { return c < 0 ? c + w : (c >= w ? c - w : c); }
+
+// one lane per query: D = do . o, then over the window P = exp(scale q.k - lse), dP = do . v, dS = P (dP - D), dq
+template <int D>
+__global__ __launch_bounds__(256) void na_bwd_dq_kernel(lc_cm_operand q, lc_cm_operand k, lc_cm_operand v,
+                                                        lc_cm_operand o, lc_cm_operand dout,
+                                                        const float* __restrict__ lse, float* dsum, float* dq,
+                                                        int heads, int h, int w, int kh, int kw, float scale) {
+    const int L = h * w;
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= L) return;
+    const int bh = blockIdx.y;
+    const int b = bh / heads, hd = bh - b * heads;
+    const int i = t / w, j = t - i * w;
+    const float* qp = q.p + b * q.bs + hd * q.hs + t;
+    const float* op = o.p + b * o.bs + hd * o.hs + t;
+    const float* gp = dout.p + b * dout.bs + hd * dout.hs + t;
+    const float* kp = k.p + b * k.bs + hd * k.hs;
+    const float* vp = v.p + b * v.bs + hd * v.hs;
+    float qr[D], g[D], acc[D];
+    float dd = 0.0f;
+#pragma unroll
+    for (int c = 0; c < D; ++c) {
+        qr[c] = qp[c * q.cs] * scale;
+        g[c] = gp[c * dout.cs];
+        dd = fmaf(g[c], op[c * o.cs], dd);
+        acc[c] = 0.0f;
+    }
+    const float ls = lse[(long long)bh * L + t];
+    dsum[(long long)bh * L + t] = dd;
+    const int r0 = na_r0(i, h, kh);
+    for (int r = r0; r < r0 + kh; ++r) {
+        for (int s = 0; s < kw; ++s) {
+            const int key = r * w + wrap(j - kw / 2 + s, w);
+            float sc = 0.0f, dp = 0.0f;
+#pragma unroll
+            for (int c = 0; c < D; ++c) {
+                sc = fmaf(qr[c], kp[c * k.cs + key], sc);
+                dp = fmaf(g[c], vp[c * v.cs + key], dp);
+            }
+            const float ds = expf(sc - ls) * (dp - dd);
+#pragma unroll
+            for (int c = 0; c < D; ++c) acc[c] = fmaf(ds, kp[c * k.cs + key], acc[c]);
+        }
+    }
+    float* dp_ = dq + (long long)bh * D * L + t;
+#pragma unroll
+    for (int c = 0; c < D; ++c) dp_[(long long)c * L] = acc[c] * scale;
+}
+
+// one lane per key: every (query row i, window slot s) whose window holds this key, in a fixed order
+template <int D>
+__global__ __launch_bounds__(256) void na_bwd_dkv_kernel(lc_cm_operand q, lc_cm_operand k, lc_cm_operand v,
+                                                         lc_cm_operand dout, const float* __restrict__ lse,
+                                                         const float* __restrict__ dsum, float* dk, float* dv,
+                                                         int heads, int h, int w, int kh, int kw, float scale) {
+    const int L = h * w;
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= L) return;
+    const int bh = blockIdx.y;
+    const int b = bh / heads, hd = bh - b * heads;
+    const int r = t / w, cc = t - r * w;
+    const float* qp = q.p + b * q.bs + hd * q.hs;
+    const float* gp = dout.p + b * dout.bs + hd * dout.hs;
+    const float* kp = k.p + b * k.bs + hd * k.hs + t;
+    const float* vp = v.p + b * v.bs + hd * v.hs + t;
+    const float* lp = lse + (long long)bh * L;
+    const float* dsp = dsum + (long long)bh * L;
+    float kr[D], vr[D], ak[D], av[D];
+#pragma unroll
+    for (int c = 0; c < D; ++c) {
+        kr[c] = kp[c * k.cs];
+        vr[c] = vp[c * v.cs];
+        ak[c] = 0.0f;
+        av[c] = 0.0f;
+    }
+    const int i0 = max(0, r - kh + 1), i1 = min(h - 1, r + kh - 1);
+    for (int i = i0; i <= i1; ++i) {
+        const int r0 = na_r0(i, h, kh);
+        if (r < r0 || r > r0 + kh - 1) continue;
+        for (int s = 0; s < kw; ++s) {
+            const int qt = i * w + wrap(cc + kw / 2 - s, w);
+            float sc = 0.0f, dp = 0.0f;
+#pragma unroll
+            for (int c = 0; c < D; ++c) {
+                sc = fmaf(qp[c * q.cs + qt] * scale, kr[c], sc);
+                dp = fmaf(gp[c * dout.cs + qt], vr[c], dp);
+            }
+            const float pw = expf(sc - lp[qt]);
+            const float ds = pw * (dp - dsp[qt]);
+#pragma unroll
+            for (int c = 0; c < D; ++c) {
+                av[c] = fmaf(pw, gp[c * dout.cs + qt], av[c]);
+                ak[c] = fmaf(ds, qp[c * q.cs + qt], ak[c]);
+            }
+        }
+    }
+    float* kop = dk + (long long)bh * D * L + t;
+    float* vop = dv + (long long)bh * D * L + t;
+#pragma unroll
+    for (int c = 0; c < D; ++c) {
+        kop[(long long)c * L] = ak[c] * scale;
+        vop[(long long)c * L] = av[c];
+    }
+}
+
+// element e of the output grid [C, H, W] of one sample: d(skip)[e] and dy at the depth-to-space source of e
+__global__ __launch_bounds__(256) void lerp_bwd_kernel(const float* __restrict__ dout, long long dout_bs,
+                                                       const float* __restrict__ alpha, float* dskip,
+                                                       long long dskip_bs, float* dy, long long dy_bs, int C, int h,
+                                                       int w, int P1, int P2) {
+    const int b = blockIdx.y;
+    const int H = h * P1, W = w * P2;
+    const long long n = (long long)C * H * W;
+    for (long long e = blockIdx.x * 256ll + threadIdx.x; e < n; e += (long long)gridDim.x * 256) {
+        const int X = (int)(e % W);
+        const long long rr = e / W;
+        const int Y = (int)(rr % H);
+        const int c = (int)(rr / H);
+        const int y = Y / P1, p1 = Y - y * P1, x = X / P2, p2 = X - x * P2;
+        const int ci = (p1 * P2 + p2) * C + c;
+        const float a = 1.0f / (1.0f + expf(-alpha[c]));
+        const float g = dout[b * dout_bs + e];
+        dskip[b * dskip_bs + e] = (1.0f - a) * g;
+        dy[b * dy_bs + ((long long)ci * h + y) * w + x] = a * g;
+    }
+}
+
+__global__ __launch_bounds__(256) void lerp_dalpha_kernel(const float* __restrict__ dout, long long dout_bs,
+                                                          const float* __restrict__ y, long long y_bs,
+                                                          const float* __restrict__ skip, long long skip_bs,
+                                                          const float* __restrict__ alpha, float* dalpha, int B,
+                                                          int C, int h, int w, int P1, int P2) {
+    __shared__ double sh[256];
+    const int c = blockIdx.x;
+    const int W = w * P2;
+    const long long plane = (long long)h * P1 * W;
+    double acc = 0.0;
+    for (int b = 0; b < B; ++b) {
+        const float* gp = dout + b * dout_bs + (long long)c * plane;
+        const float* sp = skip + b * skip_bs + (long long)c * plane;
+        for (long long e = threadIdx.x; e < plane; e += 256) {
+            const int Y = (int)(e / W), X = (int)(e - (long long)Y * W);
+            const int yy = Y / P1, p1 = Y - yy * P1, xx = X / P2, p2 = X - xx * P2;
+            const float z = y[b * y_bs + (((long long)(p1 * P2 + p2) * C + c) * h + yy) * w + xx];
+            acc = fma((double)gp[e], (double)z - (double)sp[e], acc);
+        }
+    }
+    const double s = block_sum256(acc, sh);
+    if (threadIdx.x == 0) {
+        const double a = 1.0 / (1.0 + exp(-(double)alpha[c]));
+        dalpha[c] = (float)(a * (1.0 - a) * s);
+    }
+}
+
+inline int grid_for(long long n) {
+    long long g = (n + 255) / 256;
+    return (int)(g > 4096 ? 4096 : (g < 1 ? 1 : g));
+}
+
+}  // namespace
+
+extern "C" int lc_hdit_rmsnorm_bwd(const float* x, int64_t x_bs, int64_t x_cs, const float* f, int64_t f_bs, int mode,
+                                   const float* dy, int64_t dy_bs, int64_t dy_cs, float* dx, int64_t dx_bs,
+                                   int64_t dx_cs, float* rs, float* df, int64_t df_bs, int B, int C, int L, float eps,
+                                   lc_stream_t s) {
+    if (!x || !dy || !dx || B <= 0 || C <= 0 || L <= 0 || x_cs <= 0 || dy_cs <= 0 || dx_cs <= 0 || mode < 0 ||
+        mode > 2 || !(eps > 0.0f))
+        return LC_EINVAL;
+    if ((mode != 0 && !f) || (df && (mode == 0 || !rs))) return LC_EINVAL;
+    if (B > 65535 || C > (1 << 30)) return LC_EUNSUP;
+    hipLaunchKernelGGL(rmsnorm_bwd_kernel, dim3((L + 63) / 64, B), dim3(256), 0, lc_s(s), x, (long long)x_bs,
+                       (long long)x_cs, f, (long long)f_bs, mode, dy, (long long)dy_bs, (long long)dy_cs, dx,
+                       (long long)dx_bs, (long long)dx_cs, rs, C, L, eps);
+    if (df)
+        hipLaunchKernelGGL(rmsnorm_dparam_kernel, dim3(C, mode == 1 ? B : 1), dim3(256), 0, lc_s(s), x,
+                           (long long)x_bs, (long long)x_cs, dy, (long long)dy_bs, (long long)dy_cs, rs, df,
+                           (long long)df_bs, mode, B, L);
+    return lc_launch_status();
+}
+
+extern "C" int lc_hdit_geglu_bwd(const float* x, int64_t x_bs, const float* dy, int64_t dy_bs, float* dx,
+                                 int64_t dx_bs, int B, int mid, int L, lc_stream_t s) {
+    if (!x || !dy || !dx || B <= 0 || mid <= 0 || L <= 0) return LC_EINVAL;
+    if (B > 65535) return LC_EUNSUP;
+    hipLaunchKernelGGL(geglu_bwd_kernel, dim3(grid_for((long long)mid * L), B), dim3(256), 0, lc_s(s), x,
+                       (long long)x_bs, dy, (long long)dy_bs, dx, (long long)dx_bs, mid, L);
+    return lc_launch_status();
+}
+
+extern "C" int lc_hdit_qk_prep_bwd(const float* q, int64_t q_bs, int64_t q_cs, const float* k, int64_t k_bs,
+                                   int64_t k_cs, const float* gq, int64_t gq_bs, int64_t gq_cs, const float* gk,
+                                   int64_t gk_bs, int64_t gk_cs, float* dq, int64_t dq_bs, int64_t dq_cs, float* dk,
+                                   int64_t dk_bs, int64_t dk_cs, const float* scale, const float* cos_t,
+                                   const float* sin_t, double* part, float* dscale, int B, int heads, int d, int L,
+                                   lc_stream_t s) {
+    if (!q || !k || !gq || !gk || !dq || !dk || !scale || !cos_t || !sin_t || !part || B <= 0 || heads <= 0 ||
+        L <= 0 || q_cs <= 0 || k_cs <= 0 || gq_cs <= 0 || gk_cs <= 0 || dq_cs <= 0 || dk_cs <= 0)
+        return LC_EINVAL;
+    if ((d != 32 && d != 64) || (long long)B * heads > 65535) return LC_EUNSUP;
+    const dim3 grid((L + 255) / 256, B * heads, 2);
+    if (d == 32)
+        hipLaunchKernelGGL(qk_prep_bwd_kernel<32>, grid, dim3(256), 0, lc_s(s), q, (long long)q_bs, (long long)q_cs,
+                           k, (long long)k_bs, (long long)k_cs, gq, (long long)gq_bs, (long long)gq_cs, gk,
+                           (long long)gk_bs, (long long)gk_cs, dq, (long long)dq_bs, (long long)dq_cs, dk,
+                           (long long)dk_bs, (long long)dk_cs, scale, cos_t, sin_t, part, B, heads, L);
+    else
+        hipLaunchKernelGGL(qk_prep_bwd_kernel<64>, grid, dim3(256), 0, lc_s(s), q, (long long)q_bs, (long long)q_cs,
+                           k, (long long)k_bs, (long long)k_cs, gq, (long long)gq_bs, (long long)gq_cs, gk,
+                           (long long)gk_bs, (long long)gk_cs, dq, (long long)dq_bs, (long long)dq_cs, dk,
+                           (long long)dk_bs, (long long)dk_cs, scale, cos_t, sin_t, part, B, heads, L);
+    if (dscale)
+        hipLaunchKernelGGL(qk_scale_grad_kernel, dim3(heads), dim3(256), 0, lc_s(s), part, scale, dscale, B, L);
+    return lc_launch_status();
+}
+
+extern "C" int lc_hdit_na_bwd(const lc_cm_operand* q, const lc_cm_operand* k, const lc_cm_operand* v,
+                              const lc_cm_operand* o, const lc_cm_operand* dout, const float* lse, float* dsum,
+                              float* dq, float* dk, float* dv, int B, int heads, int d, int h, int w, int kh, int kw,
+                              float scale, lc_stream_t s) {
+    if (!q || !k || !v || !o || !dout || !q->p || !k->p || !v->p || !o->p || !dout->p || !lse || !dsum || !dq ||
+        !dk || !dv || B <= 0 || heads <= 0 || h <= 0 || w <= 0 || kh <= 0 || kw <= 0)
+        return LC_EINVAL;
+    if (!(kh & 1) || !(kw & 1) || kh * kw > 81 || kh > h || kw / 2 > w) return LC_EUNSUP;
+    if ((d != 32 && d != 64) || (long long)B * heads > 65535 || (long long)h * w * d >= (1ll << 30)) return LC_EUNSUP;
+    const int L = h * w;
+    const dim3 grid((L + 255) / 256, B * heads);
+    if (d == 32) {
+        hipLaunchKernelGGL(na_bwd_dq_kernel<32>, grid, dim3(256), 0, lc_s(s), *q, *k, *v, *o, *dout, lse, dsum, dq,
+                           heads, h, w, kh, kw, scale);
+        hipLaunchKernelGGL(na_bwd_dkv_kernel<32>, grid, dim3(256), 0, lc_s(s), *q, *k, *v, *dout, lse, dsum, dk, dv,
+                           heads, h, w, kh, kw, scale);
+    } else {
+        hipLaunchKernelGGL(na_bwd_dq_kernel<64>, grid, dim3(256), 0, lc_s(s), *q, *k, *v, *o, *dout, lse, dsum, dq,
+                           heads, h, w, kh, kw, scale);
+        hipLaunchKernelGGL(na_bwd_dkv_kernel<64>, grid, dim3(256), 0, lc_s(s), *q, *k, *v, *dout, lse, dsum, dk, dv,
+                           heads, h, w, kh, kw, scale);
+    }
+    return lc_launch_status();
+}
+
+extern "C" int lc_hdit_lerp_bwd(const float* dout, int64_t dout_bs, const float* y, int64_t y_bs, const float* skip,
+                                int64_t skip_bs, const float* alpha, float* dskip, int64_t dskip_bs, float* dy,
+                                int64_t dy_bs, float* dalpha, int B, int C, int h, int w, int P1, int P2,
+                                lc_stream_t s) {
+    if (!dout || !y || !skip || !alpha || !dskip || !dy || B <= 0 || C <= 0 || h <= 0 || w <= 0 || P1 <= 0 ||
+        P2 <= 0)
+        return LC_EINVAL;
+    if (B > 65535 || (long long)C * h * w * P1 * P2 >= (1ll << 31)) return LC_EUNSUP;
+    hipLaunchKernelGGL(lerp_bwd_kernel, dim3(grid_for((long long)C * h * w * P1 * P2), B), dim3(256), 0, lc_s(s),
+                       dout, (long long)dout_bs, alpha, dskip, (long long)dskip_bs, dy, (long long)dy_bs, C, h, w, P1,
+                       P2);
+    if (dalpha)
+        hipLaunchKernelGGL(lerp_dalpha_kernel, dim3(C), dim3(256), 0, lc_s(s), dout, (long long)dout_bs, y,
+                           (long long)y_bs, skip, (long long)skip_bs, alpha, dalpha, B, C, h, w, P1, P2);
+    return lc_launch_status();
+}

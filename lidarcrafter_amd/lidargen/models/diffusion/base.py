@@ -144,13 +144,15 @@ class GaussianDiffusion(nn.Module):
     def p_loss(self, x_0, steps, loss_mask=None):
         """Loss of one denoising step (reference base.py:124-143).  With grad mode on and trainable
         parameters the denoiser builds an autograd graph over the HIP kernels
-        (lidarcrafter_amd/autograd.py: EfficientUNet this round), so `ddpm(x_0).backward()` works as in
+        (lidarcrafter_amd/autograd.py: EfficientUNet; autograd_hdit.py: HDiT in train mode), so `ddpm(x_0).backward()` works as in
         tools/train/train_lidm.py:214-265; otherwise only the value is computed."""
         loss_mask = torch.ones_like(x_0) if loss_mask is None else loss_mask
         x_t, noise = self.q_step_from_x_0(x_0, steps)
         from lidarcrafter_amd import autograd as AG
 
-        train = AG.training_active(self.model) and hasattr(self.model, "d_block1")
+        # EfficientUNet: the graph follows grad mode; HDiT: grad mode and train mode (models/dits/hdit.py)
+        hdit = hasattr(self.model, "mid_levels") and hasattr(self.model, "detokenizer")
+        train = AG.training_active(self.model) and (hasattr(self.model, "d_block1") or (hdit and self.model.training))
         with (contextlib.nullcontext() if train else torch.no_grad()):
             prediction = self.model(x_t, self.get_network_condition(steps))
         return self._masked_loss(prediction, self.get_target(x_0, steps, noise), loss_mask, steps)

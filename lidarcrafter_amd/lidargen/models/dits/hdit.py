@@ -15,7 +15,11 @@ CUDA neighbourhood-attention library; here the whole forward runs on the channel
     the channel-major positional embedding, the concatenated modulation weights -- are rebuilt when their sources
     change (address / version) and the rebuild bumps the pack epoch, so no captured step graph reads a stale table.
 
-Inference only: a forward in grad mode raises (training needs backward kernels that are not built).
+Training (lidarcrafter_amd/autograd_hdit.py): a forward builds an autograd graph over the HIP backward kernels when grad
+mode is on, something requires grad AND the module is in train mode -- the state `ddpm.train()` leaves it in, as in the
+reference's training scripts.  An eval-mode forward in grad mode still raises: the inference forward is not a graph (in-place
+q / k preparation, detached caches), and EfficientUNet's rule (the graph follows grad mode alone) would silently swap the
+sampler's inference kernels for the slower training composition wherever a caller forgot `torch.no_grad()`.
 """
 from __future__ import annotations
 
@@ -370,7 +374,15 @@ class HDiT(nn.Module):
         """x [B, C, H, W], t = log-SNR [B] (or 0-d) -> [B, C_out, H, W].  `time_features`: optional precomputed
         `self.time_features(log_snr)` (the sampler hoists them out of the steps)."""
         if AG.training_active(self, x):
-            raise NotImplementedError("HDiT training is not built")
+            if not self.training:
+                raise NotImplementedError("HDiT training is not built for eval-mode forwards: call .train(), or run "
+                                          "under torch.no_grad()")
+            if not x.is_cuda:
+                raise NotImplementedError("HDiT runs on the GPU kernels only; there is no CPU path")
+            from lidarcrafter_amd.autograd_hdit import hdit_forward
+
+            self.nfe += 1
+            return hdit_forward(self, x, t)
         if not x.is_cuda:
             raise NotImplementedError("HDiT runs on the GPU kernels only; there is no CPU path")
         B = x.shape[0]

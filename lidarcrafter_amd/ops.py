@@ -1904,6 +1904,162 @@ def hdit_fourier(t: torch.Tensor, freqs: torch.Tensor) -> torch.Tensor:
           "lc_hdit_fourier_fwd")
     return y
 
+
+# ---- HDiT training (csrc/hdit.hip lc_hdit_na_train_fwd, csrc/hdit_bwd.hip; used by autograd_hdit.py)
+def _rows_or_grid(t: torch.Tensor, name: str):
+    """(B, C, L, batch stride, channel stride) of a token grid [B, C, h, w] (contiguous samples) or of rows [M, C]."""
+    if t.dim() == 2:
+        _req(t, name)
+        if t.stride(1) != 1:
+            raise ValueError(f"`{name}`: rows need unit channel stride")
+        return t.shape[0], t.shape[1], 1, t.stride(0), 1
+    bs = _bs4(t, name)
+    B, C, H, W = t.shape
+    return B, C, H * W, bs, H * W
+
+
+def hdit_rmsnorm_bwd(x: torch.Tensor, dy: torch.Tensor, mod: Optional[torch.Tensor] = None,
+                     gain: Optional[torch.Tensor] = None, eps: float = 1e-6, want_param: bool = True):
+    """Backward of `hdit_rmsnorm` (same x, mod / gain, eps): (dx, d(mod) [B, C] or d(gain) [C] or None)."""
+    B, C, L, x_bs, x_cs = _rows_or_grid(x, "x")
+    dy = dy.contiguous()
+    if dy.shape != x.shape:
+        raise ValueError("hdit_rmsnorm_bwd: dy shaped like x")
+    _, _, _, g_bs, g_cs = _rows_or_grid(dy, "dy")
+    dx = torch.empty(x.shape, device=x.device, dtype=_F32)
+    mode, f, f_bs = 0, None, 0
+    if mod is not None:
+        _req(mod, "mod")
+        if mod.shape != (B, C) or mod.stride(1) != 1:
+            raise ValueError("hdit_rmsnorm_bwd: mod must be [B, C] with unit channel stride")
+        mode, f, f_bs = 1, mod, mod.stride(0)
+    elif gain is not None:
+        _req(gain, "gain")
+        if gain.shape != (C,) or not gain.is_contiguous():
+            raise ValueError("hdit_rmsnorm_bwd: gain must be contiguous [C]")
+        mode, f = 2, gain
+    df = rs = None
+    if want_param and mode:
+        df = torch.empty((B, C) if mode == 1 else (C,), device=x.device, dtype=_F32)
+        rs = torch.empty(B * L, device=x.device, dtype=_F32)
+    with _Timed("hdit_rmsnorm_bwd", 10.0 * B * C * L, rd=12.0 * B * C * L, wr=4.0 * B * C * L):
+        check(lib().lc_hdit_rmsnorm_bwd(x.data_ptr(), x_bs, x_cs, _p(f), f_bs, mode, dy.data_ptr(), g_bs, g_cs,
+                                        dx.data_ptr(), g_bs, g_cs, _p(rs), _p(df), C, B, C, L, float(eps), _stream()),
+              "lc_hdit_rmsnorm_bwd")
+    return dx, df
+
+
+def hdit_geglu_bwd(x: torch.Tensor, dy: torch.Tensor) -> torch.Tensor:
+    """Backward of `hdit_geglu`: x [B, 2 mid, h, w] (or rows [M, 2 mid]), dy shaped like its output -> dx."""
+    B, C2, L, x_bs, _ = _rows_or_grid(x, "x")
+    if C2 % 2:
+        raise ValueError("hdit_geglu_bwd: odd channel count")
+    dy = dy.contiguous()
+    _req(dy, "dy")
+    if dy.shape[0] != B or dy.shape[1] != C2 // 2 or dy.numel() != B * (C2 // 2) * L:
+        raise ValueError("hdit_geglu_bwd: dy shaped like the forward's output")
+    dx = torch.empty(x.shape, device=x.device, dtype=_F32)
+    with _Timed("hdit_geglu_bwd", 20.0 * B * C2 // 2 * L, rd=6.0 * B * C2 * L, wr=4.0 * B * C2 * L):
+        check(lib().lc_hdit_geglu_bwd(x.data_ptr(), x_bs, dy.data_ptr(), (C2 // 2) * L, dx.data_ptr(), C2 * L, B,
+                                      C2 // 2, L, _stream()), "lc_hdit_geglu_bwd")
+    return dx
+
+
+def hdit_qk_prep_bwd(q: torch.Tensor, k: torch.Tensor, gq: torch.Tensor, gk: torch.Tensor, heads: int,
+                     scale: torch.Tensor, cos_t: torch.Tensor, sin_t: torch.Tensor, want_scale: bool = True):
+    """Backward of `hdit_qk_prep` taken out of place: q, k the raw slices, gq / gk the gradients of the prepared q / k
+    -> (dq, dk contiguous [B, heads*d, L], d(scale) shaped like `scale` or None)."""
+    _cm3(q, "q"), _cm3(k, "k")
+    gq, gk = gq.contiguous(), gk.contiguous()
+    _cm3(gq, "gq"), _cm3(gk, "gk")
+    for n_, t_ in (("scale", scale), ("cos_t", cos_t), ("sin_t", sin_t)):
+        _req(t_, n_)
+    B, Cq, L = q.shape
+    if k.shape != q.shape or gq.shape != q.shape or gk.shape != q.shape or Cq % heads:
+        raise ValueError("hdit_qk_prep_bwd: q, k, gq, gk of one shape, channels divisible by heads")
+    d = Cq // heads
+    if scale.numel() != heads or not scale.is_contiguous():
+        raise ValueError("hdit_qk_prep_bwd: one contiguous scale per head")
+    for t_ in (cos_t, sin_t):
+        if tuple(t_.shape) != (heads, d // 2, L) or not t_.is_contiguous():
+            raise ValueError(f"hdit_qk_prep_bwd: RoPE tables must be contiguous [{heads}, {d // 2}, {L}]")
+    dq = torch.empty((B, Cq, L), device=q.device, dtype=_F32)
+    dk = torch.empty((B, Cq, L), device=q.device, dtype=_F32)
+    part = torch.empty(heads * B * 2 * L, device=q.device, dtype=torch.float64)
+    ds = torch.empty(scale.shape, device=q.device, dtype=_F32) if want_scale else None
+    with _Timed("hdit_qk_prep_bwd", 24.0 * B * Cq * L, rd=16.0 * B * Cq * L, wr=8.0 * B * Cq * L):
+        check(lib().lc_hdit_qk_prep_bwd(q.data_ptr(), q.stride(0), q.stride(1), k.data_ptr(), k.stride(0), k.stride(1),
+                                        gq.data_ptr(), gq.stride(0), gq.stride(1), gk.data_ptr(), gk.stride(0),
+                                        gk.stride(1), dq.data_ptr(), Cq * L, L, dk.data_ptr(), Cq * L, L,
+                                        scale.data_ptr(), cos_t.data_ptr(), sin_t.data_ptr(), part.data_ptr(), _p(ds),
+                                        B, heads, d, L, _stream()), "lc_hdit_qk_prep_bwd")
+    return dq, dk, ds
+
+
+def hdit_na_train(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, h: int, w: int, kernel_size,
+                  scale: float = 1.0):
+    """`hdit_na` that also returns the log-sum-exp per (sample, head, query), [B * heads, h * w] (o bit-identical)."""
+    kh, kw = kernel_size
+    for n_, t_ in (("q", q), ("k", k), ("v", v)):
+        _cm3(t_, n_)
+    B, Cq, L = q.shape
+    if k.shape != q.shape or v.shape != q.shape or L != h * w or Cq % heads:
+        raise ValueError("hdit_na_train: q, k, v of one [B, heads*d, h*w] shape")
+    d = Cq // heads
+    out = torch.empty((B, Cq, L), device=q.device, dtype=_F32)
+    lse = torch.empty((B * heads, L), device=q.device, dtype=_F32)
+    with _Timed("hdit_na", 4.0 * B * Cq * L * kh * kw, rd=12.0 * B * Cq * L, wr=4.0 * B * Cq * L):
+        check(lib().lc_hdit_na_train_fwd(_cm_operand(q, d), _cm_operand(k, d), _cm_operand(v, d), out.data_ptr(),
+                                         out.stride(0), d * out.stride(1), out.stride(1), lse.data_ptr(), B, heads, d,
+                                         h, w, kh, kw, float(scale), _stream()), "lc_hdit_na_train_fwd")
+    return out, lse
+
+
+def hdit_na_bwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, o: torch.Tensor, do: torch.Tensor,
+                lse: torch.Tensor, heads: int, h: int, w: int, kernel_size, scale: float = 1.0):
+    """Backward of `hdit_na_train` -> (dq, dk, dv), contiguous [B, heads*d, h*w]."""
+    kh, kw = kernel_size
+    do = do if (do.dim() == 3 and do.stride(2) == 1) else do.contiguous()
+    for n_, t_ in (("q", q), ("k", k), ("v", v), ("o", o), ("do", do), ("lse", lse)):
+        _req(t_, n_)
+    for n_, t_ in (("q", q), ("k", k), ("v", v), ("o", o), ("do", do)):
+        _cm3(t_, n_)
+    B, Cq, L = q.shape
+    if any(t_.shape != q.shape for t_ in (k, v, o, do)) or L != h * w or Cq % heads:
+        raise ValueError("hdit_na_bwd: q, k, v, o, do of one [B, heads*d, h*w] shape")
+    if tuple(lse.shape) != (B * heads, L) or not lse.is_contiguous():
+        raise ValueError("hdit_na_bwd: lse must be contiguous [B * heads, h * w]")
+    d = Cq // heads
+    dq, dk, dv = (torch.empty((B, Cq, L), device=q.device, dtype=_F32) for _ in range(3))
+    dsum = torch.empty(B * heads * L, device=q.device, dtype=_F32)
+    with _Timed("hdit_na_bwd", 12.0 * B * Cq * L * kh * kw, rd=20.0 * B * Cq * L, wr=12.0 * B * Cq * L):
+        check(lib().lc_hdit_na_bwd(_cm_operand(q, d), _cm_operand(k, d), _cm_operand(v, d), _cm_operand(o, d),
+                                   _cm_operand(do, d), lse.data_ptr(), dsum.data_ptr(), dq.data_ptr(), dk.data_ptr(),
+                                   dv.data_ptr(), B, heads, d, h, w, kh, kw, float(scale), _stream()), "lc_hdit_na_bwd")
+    return dq, dk, dv
+
+
+def hdit_lerp_bwd(dout: torch.Tensor, y: torch.Tensor, skip: torch.Tensor, alpha: torch.Tensor, p1: int, p2: int,
+                  want_alpha: bool = True):
+    """Backward of `depth_to_space(y, p1, p2, skip, alpha)`: (dy [B, C*p1*p2, h, w], dskip, d(alpha) [C] or None)."""
+    y_bs, s_bs = _bs4(y, "y"), _bs4(skip, "skip")
+    dout = dout.contiguous()
+    _req(alpha, "alpha")
+    B, Cx, h, w = y.shape
+    C = Cx // (p1 * p2)
+    shape = (B, C, h * p1, w * p2)
+    if Cx % (p1 * p2) or tuple(dout.shape) != shape or tuple(skip.shape) != shape or alpha.shape != (C,) or \
+            not alpha.is_contiguous():
+        raise ValueError("hdit_lerp_bwd: y [B, C*p1*p2, h, w], dout / skip [B, C, h*p1, w*p2], alpha contiguous [C]")
+    dy = torch.empty(y.shape, device=y.device, dtype=_F32)
+    dskip = torch.empty(shape, device=y.device, dtype=_F32)
+    da = torch.empty(C, device=y.device, dtype=_F32) if want_alpha else None
+    n = C * h * w * p1 * p2
+    check(lib().lc_hdit_lerp_bwd(dout.data_ptr(), n, y.data_ptr(), y_bs, skip.data_ptr(), s_bs, alpha.data_ptr(),
+                                 dskip.data_ptr(), n, dy.data_ptr(), n, _p(da), B, C, h, w, p1, p2, _stream()),
+          "lc_hdit_lerp_bwd")
+    return dy, dskip, da
+
 # Keys / values in unit form (csrc/attention_units.hip): the fp16 hi / lo split of the attention operands made once per
 # step -- or once per CONDITION for the step-invariant parts -- instead of once per query block inside the kernel.
 # LC_ATTN_UNITS=0 keeps ObjectAwareCrossAttention on lc_attention_f16x2_fwd.
