@@ -306,12 +306,21 @@ class ContinuousTimeGaussianDiffusion(base.GaussianDiffusion):
                  noise=torch.empty_like(x).contiguous() if st["needs_noise"] else None, other=None)
         cond = st["cond"]
         if cond is not None and isinstance(cond["other_condition"], torch.Tensor):
-            g["other"] = cond["other_condition"].clone()       # the step reads the condition from the entry's buffer
-            cond["other_condition"] = g["other"]
+            # the step reads the condition from the entry's buffer: the run goes on with a dict of its own that names the
+            # buffer -- the caller's dict keeps its tensor (it may be used again after other conditions went through the
+            # buffer)
+            g["other"] = cond["other_condition"].clone()
+            st["cond"] = dict(cond, other_condition=g["other"])
         row.copy_(table[st["i"]])
         graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            self._step_body(st, g["lam"], g["tf"], g["coef"], g["noise"])
+        try:
+            with torch.cuda.graph(graph):
+                self._step_body(st, g["lam"], g["tf"], g["coef"], g["noise"])
+        except Exception:
+            st["cond"] = cond
+            raise
+        if st["cond"] is not cond:
+            cond.update(dict(time_condition=g["lam"]))         # what the step leaves in the caller's dict
         g["graph"] = graph
         return g
 
@@ -329,11 +338,11 @@ class ContinuousTimeGaussianDiffusion(base.GaussianDiffusion):
         if table.shape[1] != shared["P"]:
             return None
         cond = st["cond"]
-        if shared["other"] is not None:
-            shared["other"].copy_(cond["other_condition"])
-            cond["other_condition"] = shared["other"]
         if cond is not None:
             cond.update(dict(time_condition=shared["lam"]))    # what an eager first step leaves in the caller's dict
+        if shared["other"] is not None:
+            shared["other"].copy_(cond["other_condition"])     # always from the caller's own tensor, see _capture
+            st["cond"] = dict(cond, other_condition=shared["other"])
         if shared["x"].data_ptr() != st["x"].data_ptr():
             st["x"] = K.copy_into(shared["x"], st["x"])
         return dict(shared, table=table)
@@ -346,6 +355,14 @@ class ContinuousTimeGaussianDiffusion(base.GaussianDiffusion):
         cache[key] = g
         while len(cache) > self.graph_cache_size:
             cache.pop(next(iter(cache)))
+
+    def clear_graph_cache(self) -> None:
+        """Drop every graph this sampler keeps between calls, with the memory pools behind them: the captured steps, the
+        denoiser's condition-operand graph and the condition model's core graph.  The next run captures again."""
+        _GRAPH_CACHES.pop(self, None)
+        for m, name in ((self.model, "_prep"), (self.condition_model, "_core_graph")):
+            if isinstance(m, nn.Module) and m.__dict__.get(name) is not None:
+                m.__dict__[name] = None
 
     @torch.compiler.disable
     @torch.inference_mode()

@@ -126,12 +126,15 @@ class LayoutTransformerEncoder(nn.Module):
 
     def _patch_embedding(self, key, dev):
         """Embedding of the feature-map cells of one attention level: a function of `obj_bbox_2d_embedding` alone (the
-        reference recomputes it per forward, layout_encoder.py:228-237).  Kept per (weights, device) outside grad mode."""
+        reference recomputes it per forward, layout_encoder.py:228-237).  Kept per (weights, device, inference mode) outside
+        grad mode: a tensor made inside a sampling run is an inference tensor, which autograd refuses to save, so a training
+        step of the denoiser with this layer frozen gets a tensor of its own."""
         lin = self.obj_bbox_2d_embedding
         if torch.is_grad_enabled() and (lin.weight.requires_grad or lin.bias.requires_grad):
             cells = self.image_patch_bbox_embedding[key].to(dev, self.dtype)
             return lin(cells).t().contiguous(), None
-        tag = (key, str(dev), lin.weight.data_ptr(), lin.weight._version, lin.bias.data_ptr(), lin.bias._version)
+        tag = (key, str(dev), lin.weight.data_ptr(), lin.weight._version, lin.bias.data_ptr(), lin.bias._version,
+               torch.is_inference_mode_enabled())
         cache = self.__dict__.setdefault("_patch_cache", {})
         ent = cache.get(key)
         if ent is None or ent[0] != tag:

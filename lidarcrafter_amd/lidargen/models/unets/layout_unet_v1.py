@@ -585,6 +585,13 @@ class LayoutUnetV1(nn.Module):
         lay = dict(lay)
         lay.update(st["inp"])
         st["lay"] = lay
+        # the graph writes to the ADDRESSES of the tensors the layers held when it was captured (`dst` keeps them alive): a
+        # forward on a condition that never came through here (outside inference mode, another batch size) gives a layer
+        # new ones -- the graph would then fill tensors nobody reads.  Drop it, compute eagerly into whatever the layers
+        # hold now, capture again at the next condition.
+        if not self._holds_targets(layers, st.get("dst")):
+            st["graph"] = None if st["graph"] is not False else False
+            st["runs"], st["dst"] = 0, None
         if st["graph"] is None and st["runs"] >= 1:
             try:
                 g = torch.cuda.CUDAGraph()
@@ -597,13 +604,33 @@ class LayoutUnetV1(nn.Module):
 
                 warnings.warn(f"HIP graph capture of the condition operands failed ({e!r}); staying eager")
                 st["graph"] = False
+            st["dst"] = self._operand_targets(layers)
         if st["graph"]:
             st["graph"].replay()
             return True
         for m in layers:
             m.condition_operands(lay, refresh=True)
         st["runs"] += 1
+        st["dst"] = self._operand_targets(layers)
         return True
+
+    @staticmethod
+    def _operand_targets(layers):
+        """Per attention layer: the four operand tensors and the unit-form buffer its `_cond_cache` holds."""
+        out = []
+        for m in layers:
+            c = m._cond_cache
+            out.append(None if c is None else tuple(c[1:5]) + (c[8].buf if len(c) > 8 and c[8] is not None else None,))
+        return out
+
+    @classmethod
+    def _holds_targets(cls, layers, dst) -> bool:
+        if dst is None:
+            return False
+        now = cls._operand_targets(layers)
+        return len(now) == len(dst) and all(
+            a is not None and b is not None and len(a) == len(b) and all(s is t for s, t in zip(a, b))
+            for a, b in zip(now, dst))
 
     def _static_condition(self, lay):
         """The static view of the condition `prepare_condition` last saw, when `lay` is that condition."""
