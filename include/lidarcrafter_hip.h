@@ -852,6 +852,46 @@ int lc_rbf_kernel_sum(const float* p, const float* q, int M, int Mq, int D, floa
 int lc_chamfer3d_fwd(const float* xyz1, const float* xyz2, int B, int N, int M, float* dist1,
                      int32_t* idx1, float* dist2, int32_t* idx2, lc_stream_t s);
 
+/* ---------------------------------------------------------------------------------------------
+ * Scene-graph layout generator (lidargen/models/unets/unet_1d.py UNet1DModel on a signal of length 1, graph.py
+ * GraphTripleConv): skinny dense layers on row-major activations, csrc/layout_gen.hip, DESIGN.md section 5h.
+ *
+ * lc_row_segment: `width` columns of a gathered activation matrix; row m of the matrix reads row idx[m] (m when idx is
+ *   NULL) of p, rows `ld` floats apart.  Up to three segments side by side make the K axis ([s | p | o] rows of a
+ *   triple, [h | skip]).  The entry points do NOT check index VALUES (idx[], vec_row[], slots[], row_ptr[]): the caller
+ *   guarantees that every one names a row of its tensor (unet_1d._Plan checks them on the host, once per call).
+ * lc_skinny_gemm_fwd: parts[c][m][n] = sum over chunk c of X[m,k] w[n,k] (w in nn.Linear layout [N, K], fp32 FMA).
+ *   K is summed in chunks of 128 in ascending order; nparts = lc_skinny_parts(M, N, K) is either the chunk count (every
+ *   chunk a block of its own: the weight stream spreads over the chip) or 1 (the block adds the chunk sums itself, in
+ *   the same order).  Both forms give the same bits, for every M.
+ * lc_skinny_combine_fwd: y[m,n] = act(sum_c parts[c][m][n] + bias[n]) + vec[vec_row[m]][n] + res[m][n];
+ *   act 0 none, 1 ReLU, 2 GEGLU (N even, y has N/2 columns: a * gelu(gate), gate = columns N/2 ...).  bias, vec, res may
+ *   be NULL; vec_row NULL reads row 0 of vec for every m.
+ * lc_rowprep_fwd: y[m, :C] = [SiLU](norm(row m of the segments)); G > 0: statistics over G groups of C / G columns
+ *   (GroupNorm on [M, C, 1]; G = 1: LayerNorm), biased variance, affine gamma / beta (NULL: none); G = 0: no norm
+ *   (a plain gathered concatenation when silu is 0 too).  C <= 4096.
+ * lc_graph_pool_fwd: y[o, :H] = (sum over slots[row_ptr[o] .. row_ptr[o+1]) of t[slot >> 1, (slot & 1 ? o_col : s_col) + h])
+ *   / max(count, 1), summed in the order of slots[] -- no atomics, the result does not depend on scheduling.
+ * lc_time_embed_fwd: y[u] = [cos(t[u] freqs) | sin(t[u] freqs)], freqs [half] (nn.py timestep_embedding).
+ * ------------------------------------------------------------------------------------------- */
+typedef struct lc_row_segment {
+    const float* p;
+    const int32_t* idx;
+    int64_t ld;
+    int32_t width;
+} lc_row_segment;
+int64_t lc_skinny_parts(int M, int N, int K);
+int lc_skinny_gemm_fwd(const lc_row_segment* segs, int nseg, const float* w, float* parts, int M, int N, int K,
+                       int nparts, lc_stream_t s);
+int lc_skinny_combine_fwd(const float* parts, int nparts, const float* bias, int act, const float* vec, int64_t vec_ld,
+                          const int32_t* vec_row, const float* res, int64_t res_ld, float* y, int64_t y_ld, int M, int N,
+                          lc_stream_t s);
+int lc_rowprep_fwd(const lc_row_segment* segs, int nseg, float* y, int64_t y_ld, int M, int C, int G, float eps,
+                   const float* gamma, const float* beta, int silu, lc_stream_t s);
+int lc_graph_pool_fwd(const float* t, int64_t t_ld, int s_col, int o_col, const int32_t* row_ptr, const int32_t* slots,
+                      float* y, int64_t y_ld, int O, int H, lc_stream_t s);
+int lc_time_embed_fwd(const float* t, const float* freqs, float* y, int U, int half, lc_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -35,6 +35,14 @@ class GnStatsInput(C.Structure):
 _gs = C.POINTER(GnStatsInput)
 
 
+class RowSegment(C.Structure):
+    """struct lc_row_segment: `width` columns of a gathered activation matrix (pointer, optional row index, row stride)."""
+    _fields_ = [("p", vp), ("idx", vp), ("ld", i64), ("width", i32)]
+
+
+_rs = C.POINTER(RowSegment)
+
+
 class ConvRange(C.Structure):
     """struct lc_conv_range: device-resident pre-scale + running amax of one conv layer's input."""
     _fields_ = [("x_scale", f32), ("x_unscale", f32), ("amax_scaled", f32), ("reserved", f32)]
@@ -173,6 +181,12 @@ SIGNATURES = {
     "lc_compact_scratch_elems": (i64, [i32]),
     "lc_compact_points": (i32, [vp, vp, i32, i32, vp, vp, vp, vp, vp]),
     "lc_points_in_boxes_index": (i32, [vp, vp, i32, i32, i32, f32, vp, vp]),
+    "lc_skinny_parts": (i64, [i32, i32, i32]),
+    "lc_skinny_gemm_fwd": (i32, [_rs, i32, vp, vp, i32, i32, i32, i32, vp]),
+    "lc_skinny_combine_fwd": (i32, [vp, i32, vp, i32, vp, i64, vp, vp, i64, vp, i64, i32, i32, vp]),
+    "lc_rowprep_fwd": (i32, [_rs, i32, vp, i64, i32, i32, i32, f32, vp, vp, i32, vp]),
+    "lc_graph_pool_fwd": (i32, [vp, i64, i32, i32, vp, vp, vp, i64, i32, i32, vp]),
+    "lc_time_embed_fwd": (i32, [vp, vp, vp, i32, i32, vp]),
 }
 
 _lib = None

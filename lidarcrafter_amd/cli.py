@@ -12,6 +12,10 @@ random initialisation used by the tests.  Layout-conditioned configs take a synt
 `--cfg meanflow-nusc` samples the MeanFlow generator (inference.setup_model_flow's model) in `--flow_steps` network
 calls (default 1: the reference's one-step `z - model(z, 1, 0)`); `--mode` / `--sampling_steps` do not apply to it, and
 it runs on rank 0 alone (the data-parallel helper drives the diffusion samplers' interface).
+`--cfg nuscenes-layout` samples the scene-graph layout generator on `--batch_size` synthetic scenes
+(lidarcrafter_amd.testing.synth_scene_graph_batch with its synthetic vocabulary and stand-in CLIP features, or the
+collated batch dict of --batch_pt, whose `vocab` entry is then required) on rank 0 and writes `<out>/layout_boxes.pt` =
+{"boxes": float32 [O, 20], "obj_to_scene": int64 [O]}.
 Output per rank-0: `<out>/samples.pt` = float32 [N,5,H,W] (metric depth, x, y, z, reflectance), the
 tensor sample_and_save_cond.py:119-124,157-159 saves per sample."""
 from __future__ import annotations
@@ -60,6 +64,11 @@ def main(argv=None):
 
     cfg = CONFIGS[args.cfg]()
     cfg.resume = args.ckpt
+    if cfg.model.architecture == "unet_1d":
+        _sample_layout_gen(args, cfg, inference, device, rank)
+        if dist_on:
+            dist.destroy_process_group()
+        return
     if hasattr(cfg, "flow"):
         _sample_flow(args, cfg, inference, device, rank, world, seeded_fill, seeded_fill_qk_gains)
         if dist_on:
@@ -96,6 +105,39 @@ def main(argv=None):
               f"{dt:.2f} s ({args.sampling_steps / dt:.1f} denoising-steps/s) -> {args.out}/samples.pt")
     if dist_on:
         dist.destroy_process_group()
+
+
+def _sample_layout_gen(args, cfg, inference, device, rank):
+    """Scene-graph layout generator: one `sample()` over all scenes of the batch on rank 0."""
+    if rank != 0:
+        return
+    from lidarcrafter_amd.testing import LAYOUT_GEN_VOCAB, seeded_fill, seeded_fill_layout_gen, synth_scene_graph_batch
+
+    if args.batch_pt:
+        batch = torch.load(args.batch_pt, map_location="cpu")
+        if "vocab" not in batch:
+            raise SystemExit("--batch_pt for nuscenes-layout must hold the dataset's `vocab` next to `scenegraph_input`")
+        cfg.condition_model.params["vocab"] = batch["vocab"]
+    else:
+        batch = synth_scene_graph_batch(args.batch_size, seed=args.seed, manipulate=True)
+        cfg.condition_model.params["vocab"] = LAYOUT_GEN_VOCAB
+    ddpm = inference.load_model_layout_duffusion_training(cfg)[0]
+    if args.ckpt is None:
+        seeded_fill(ddpm, salt=100)
+        seeded_fill_layout_gen(ddpm, salt=100)
+    ddpm = ddpm.eval().to(device)
+    dec = batch["scenegraph_input"]["decoder"]
+    rng = [torch.Generator().manual_seed(args.seed + i) for i in range(dec["objs"].numel())]
+    t0 = time.perf_counter()
+    boxes = ddpm.sample({"scenegraph_input": batch["scenegraph_input"]}, args.sampling_steps, progress=False, rng=rng,
+                        mode=args.mode)
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    os.makedirs(args.out, exist_ok=True)
+    torch.save({"boxes": boxes.cpu(), "obj_to_scene": dec["obj_to_scene"].cpu()}, os.path.join(args.out, "layout_boxes.pt"))
+    print(f"{args.cfg}: {boxes.shape[0]} objects / {dec['tripltes'].shape[0]} triples in {args.batch_size} scenes, "
+          f"{args.sampling_steps} {args.mode} steps, {dt:.2f} s ({args.sampling_steps / dt:.1f} denoising-steps/s) -> "
+          f"{args.out}/layout_boxes.pt")
 
 
 def _sample_flow(args, cfg, inference, device, rank, world, seeded_fill, seeded_fill_qk_gains):

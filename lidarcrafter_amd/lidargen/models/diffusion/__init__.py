@@ -13,6 +13,5 @@ def _out_of_scope(name, why):
 
 
 # registry names of the reference (models/diffusion/__init__.py:1-6) must resolve
-CondContinuousLayoutGaussianDiffusion = _out_of_scope(
-    "CondContinuousLayoutGaussianDiffusion", "diffusion over per-object layout vectors")
+from .continuous_layout_cond import CondContinuousLayoutGaussianDiffusion  # noqa: E402
 from .continuous_time_1d_cond import CondContinuousLayoutGaussianDiffusion1D  # noqa: E402

@@ -1,7 +1,7 @@
 """Denoiser registry: the 14 names of the reference (lidargen/models/unets/__init__.py:15-30).
 On the hot path: efficient_unet, layout_unet_v1, layout_encoder, the foreground-object branch
 of SURVEY.md §8f-3 (point_unet, object_gen_encoder) and, beyond SURVEY.md §8, the MeanFlow generator
-(mf_efficient_unet).  Everything else is OUT OF SCOPE
+(mf_efficient_unet) and the scene-graph layout generator (unet_1d, scene_graph).  Everything else is OUT OF SCOPE
  and resolves to a stub whose constructor says so."""
 from .efficient_mf_unet import MFEfficientUNet
 from .efficient_unet import EfficientUNet
@@ -26,8 +26,8 @@ except ImportError:  # pragma: no cover - only while the conditional path is bei
 LayoutTransformerEncoderV5 = _stub("LayoutTransformerEncoderV5", "CLIP-text box encoder variant")
 LayoutUnet = _stub("LayoutUnet", "older variant of LayoutUnetV1 (no ring conv)")
 EfficientUNetCond = _stub("EfficientUNetCond", "dict-style time-arg variant of EfficientUNet")
-UNet1DModel = _stub("UNet1DModel", "1-D layout generator")
-SceneGraph = _stub("SceneGraph", "scene-graph GCN of the layout generator")
+from .scene_graph import SceneGraph  # noqa: E402
+from .unet_1d import UNet1DModel  # noqa: E402
 SpatialRescaler = _stub("SpatialRescaler", "LDM helper")
 Identity = _stub("Identity", "LDM helper")
 OpenAIUNetModel = _stub("OpenAIUNetModel", "LDM-style UNet")

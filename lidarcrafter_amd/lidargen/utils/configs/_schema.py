@@ -228,15 +228,24 @@ NUSC_HDIT_Config = make_config(
                       positional_embedding="learnable_embedding", ring=True),
     training=dict(num_steps=2_560_000, steps_save_model=100_000, lr_warmup_steps=80_000))
 
-# Registry names whose generators are OUT OF SCOPE (rows 3c, 5, stale KITTI
+# Registry names whose generators are OUT OF SCOPE (row 3c, stale KITTI
 # config).  They resolve to config objects; building their models raises NotImplementedError.
 KITTI_Config_ = make_config("KITTI_Config_", model_arch="efficient_unet",
                             model_params=_merge(UNCOND_UNET, base_channels=128),
                             data=dict(dataset="kitti_360", resolution=(64, 1024),
                                       fov_up=3.0, fov_down=-25.0))
-NUSC_Layout_Config = make_config("NUSC_Layout_Config", model_arch="unet_1d", model_params={},
-                                 cond_arch="scene_graph", cond_params={},
-                                 data=dict(task="layout_generation"))
+# scene-graph layout generator (option_nusc_layout.py): UNet1DModel over one 20-vector per object, condition model
+# SceneGraph.  `cond_params` has no `vocab`: the caller adds the dataset's (tools/generate/generate_layout.py:23).
+LAYOUT_GEN_UNET = dict(dims=1, in_channels=20, out_channels=20, model_channels=512, channel_mult=[1, 1, 1, 1],
+                       num_res_blocks=2, attention_resolutions=[4, 2], num_heads=8, use_spatial_transformer=True,
+                       transformer_depth=1, conditioning_key="crossattn", concat_dim=1280, crossattn_dim=1280,
+                       use_checkpoint=True, enable_t_emb=True)
+LAYOUT_GEN_SCENE_GRAPH = dict(embedding_dim=64, gconv_pooling="avg", gconv_num_layers=5, mlp_normalization="batch",
+                              separated=True, replace_latent=True, residual=True, use_angles=True, use_clip=True)
+NUSC_Layout_Config = make_config("NUSC_Layout_Config", model_arch="unet_1d", model_params=LAYOUT_GEN_UNET,
+                                 cond_arch="scene_graph", cond_params=LAYOUT_GEN_SCENE_GRAPH,
+                                 data=dict(task="layout_generation", custom_collate_fn=True),
+                                 diffusion=dict(clip_sample=False), training=_T50)
 # foreground-object branch (option_nusc_object.py): PointUNet over [1024, 4] object points
 NUSC_Object_Config = make_config(
     "NUSC_Object_Config", model_arch="point_unet", model_params=dict(point_dim=4, cond_dims=768),

@@ -11,7 +11,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from ..models.diffusion import (CondContinuousLayoutGaussianDiffusion1D,
+from ..models.diffusion import (CondContinuousLayoutGaussianDiffusion, CondContinuousLayoutGaussianDiffusion1D,
                                 CondContinuousTimeGaussianDiffusion,
                                 ContinuousTimeGaussianDiffusion, DiscreteTimeGaussianDiffusion)
 from ..models.dits import __all__ as __all_dits__
@@ -106,6 +106,28 @@ def load_model_object_duffusion_training(cfg: object):
         model=model, condition_model=cond, loss_type=d.loss_type,
         prediction_type=d.prediction_type, noise_schedule=d.noise_schedule,
         clip_sample=d.clip_sample)
+    ckpt_path = getattr(cfg, "resume", None)
+    if ckpt_path is None:
+        return ddpm, model
+    ckpt = torch.load(ckpt_path, map_location="cpu")
+    ddpm.load_state_dict(ckpt["ema_weights"])
+    ddpm.eval()
+    return ddpm, model, ckpt["global_step"], ckpt["optimizer"], ckpt["lr_scheduler"]
+
+
+def load_model_layout_duffusion_training(cfg: object):
+    """Scene-graph layout generator (reference inference.py:346-368): -> (ddpm, model) or, when cfg.resume is a
+    checkpoint path, (ddpm, model, global_step, optimizer_state, lr_state).  `cfg.condition_model.params` must carry the
+    dataset's `vocab` (tools/generate/generate_layout.py:23)."""
+    if "vocab" not in cfg.condition_model.params:
+        raise ValueError("cfg.condition_model.params['vocab'] is missing: the scene-graph condition model sizes its "
+                         "embedding tables from the dataset's vocabulary")
+    model = __all_unets__[cfg.model.architecture](**cfg.model.params)
+    cond = __all_unets__[cfg.condition_model.architecture](**cfg.condition_model.params)
+    d = cfg.diffusion
+    ddpm = CondContinuousLayoutGaussianDiffusion(
+        model=model, condition_model=cond, loss_type=d.loss_type, prediction_type=d.prediction_type,
+        noise_schedule=d.noise_schedule, clip_sample=d.clip_sample)
     ckpt_path = getattr(cfg, "resume", None)
     if ckpt_path is None:
         return ddpm, model

@@ -207,3 +207,94 @@ def synth_text_features(seed: int = 77) -> dict:
     f = torch.randn(8, 512, generator=g)
     f = f / f.norm(dim=1, keepdim=True)
     return {n: f[i] for i, n in enumerate(names)}
+
+
+@torch.no_grad()
+def seeded_fill_layout_gen(module: torch.nn.Module, salt: int = 0) -> torch.nn.Module:
+    """The layout generator's tensors `seeded_fill` leaves degenerate, keyed by their state_dict name; call after
+    `seeded_fill`: BatchNorm running statistics (mean 0.1 r, variance in [0.5, 1.5]; a fresh module has 0 / 1, which
+    hides a wrong fold) and the embedding tables at 0.5 r (`seeded_fill` scales them by 1 / sqrt(width))."""
+    for key, p in list(module.named_parameters()) + list(module.named_buffers()):
+        g = _gen_for(key, salt + 1)
+        if key.endswith("running_mean"):
+            v = 0.1 * torch.randn(p.shape, generator=g)
+        elif key.endswith("running_var"):
+            v = 0.5 + torch.rand(p.shape, generator=g)
+        elif "embeddings" in key and key.endswith("weight") and "box_embeddings" not in key:
+            v = 0.5 * torch.randn(p.shape, generator=g)
+        else:
+            continue
+        p.copy_(v.to(device=p.device, dtype=p.dtype))
+    return module
+
+
+LAYOUT_GEN_VOCAB = {
+    "object_idx_to_name": ["__scene__", "car", "truck", "construction_vehicle", "bus", "trailer", "motorcycle", "bicycle",
+                           "pedestrian"],
+    "pred_idx_to_name": ["__in_scene__", "front", "behind", "left", "right", "close by", "bigger than", "smaller than"],
+}
+
+
+def synth_scene_graph_batch(n_scenes: int, seed: int, manipulate: bool = False) -> dict:
+    """Synthetic collated batch of the scene-graph layout generator, with the key names of the reference's collate
+    (nuscenes_dataset.py:520-631, `tripltes` included): {'scenegraph_input': {'encoder': {...}, 'decoder': {...},
+    'missing_nodes', 'manipulated_subs', 'manipulated_objs'}}.  Scenes are ragged (3 + (seed + i) % 7 objects), the last
+    object of every scene appears in no triple, text / relationship features are 512-d unit-norm stand-ins for the CLIP
+    features (one per class / predicate of LAYOUT_GEN_VOCAB), boxes are [O, 40] = 20 values in (-1, 1) + their loss
+    mask.  manipulate=True: scene 0's encoder graph lacks one node of the decoder graph (an added node); the encoder
+    graph of the last scene carries another predicate on one triple (a manipulated relationship) -- with one scene both
+    happen in it."""
+    import numpy as np
+
+    g = np.random.default_rng(seed)
+    n_cls, n_pred = len(LAYOUT_GEN_VOCAB["object_idx_to_name"]), len(LAYOUT_GEN_VOCAB["pred_idx_to_name"])
+    tg = torch.Generator().manual_seed(1000 + seed)
+    cls_feat = torch.randn(n_cls, 512, generator=tg)
+    cls_feat = cls_feat / cls_feat.norm(dim=1, keepdim=True)
+    rel_feat = torch.randn(n_pred, 512, generator=tg)
+    rel_feat = rel_feat / rel_feat.norm(dim=1, keepdim=True)
+    enc = {k: [] for k in ("objs", "tripltes", "boxes", "obj_to_scene", "triple_to_scene")}
+    dec = {k: [] for k in enc}
+    missing, man_s, man_o = [], [], []
+    enc_off = dec_off = 0
+    for i in range(n_scenes):
+        n = 3 + (seed + i) % 7
+        objs = g.integers(1, n_cls, n)
+        boxes = np.concatenate([g.uniform(-1, 1, (n, 20)), (g.uniform(0, 1, (n, 20)) < 0.8).astype(np.float64)], 1)
+        pairs = [(a, b) for a in range(n - 1) for b in range(n - 1) if a != b]      # object n-1: in no triple
+        pick = g.permutation(len(pairs))[:max(2, min(len(pairs), 2 * n))]
+        tri = np.array([[pairs[j][0], g.integers(1, n_pred), pairs[j][1]] for j in sorted(pick)], np.int64)
+        e_objs, e_boxes, e_tri = objs.copy(), boxes.copy(), tri.copy()
+        if manipulate and i == 0:
+            a = int(tri[0, 0])                                       # a node with at least one triple is "added"
+            keep = np.array([j for j in range(n) if j != a])
+            remap = {int(j): k for k, j in enumerate(keep)}
+            e_objs, e_boxes = objs[keep], boxes[keep]
+            e_tri = np.array([[remap[int(s)], p, remap[int(o)]] for s, p, o in tri if s != a and o != a], np.int64)
+            if len(e_tri) == 0:
+                e_tri = np.array([[0, 1, 1]], np.int64)
+            missing.append(enc_off + a)
+        if manipulate and i == n_scenes - 1:
+            k = len(e_tri) - 1
+            e_tri[k, 1] = 1 + (e_tri[k, 1] % (n_pred - 1))           # another predicate on the encoder side
+            man_s.append(enc_off + int(e_tri[k, 0]))
+            man_o.append(enc_off + int(e_tri[k, 2]))
+        for d, (o_, t_, b_, off) in ((enc, (e_objs, e_tri, e_boxes, enc_off)), (dec, (objs, tri, boxes, dec_off))):
+            t_ = t_.copy()
+            t_[:, 0] += off
+            t_[:, 2] += off
+            d["objs"].append(torch.from_numpy(o_.astype(np.int64)))
+            d["tripltes"].append(torch.from_numpy(t_))
+            d["boxes"].append(torch.from_numpy(b_.astype(np.float32)))
+            d["obj_to_scene"].append(torch.full((len(o_),), i, dtype=torch.int64))
+            d["triple_to_scene"].append(torch.full((len(t_),), i, dtype=torch.int64))
+        enc_off += len(e_objs)
+        dec_off += n
+    out = {}
+    for name, d in (("encoder", enc), ("decoder", dec)):
+        c = {k: torch.cat(v) for k, v in d.items()}
+        c["text_feats"] = cls_feat[c["objs"]].clone()
+        c["rel_feats"] = rel_feat[c["tripltes"][:, 1]].clone()
+        out[name] = c
+    out.update(missing_nodes=missing, manipulated_subs=man_s, manipulated_objs=man_o)
+    return {"scenegraph_input": out}
