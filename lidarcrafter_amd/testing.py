@@ -90,6 +90,44 @@ def rel_l2(a: torch.Tensor, b: torch.Tensor) -> float:
     return float((a - b).norm() / b.norm().clamp_min(1e-30))
 
 
+def error_profiles(got: torch.Tensor, ref: torch.Tensor, keeps, min_elems: int = 64) -> dict:
+    """Relative-L2 error of `got` against the float64 `ref`, resolved by slice.  A fault confined to n of N outputs is
+    diluted by sqrt(n / N) in the whole-tensor figure; a profile along the axis that isolates it shows it undiluted.
+
+    keeps: tuples of kept axes, e.g. ((0,), (1,), (2,), (3,), (2, 3)) = sample, channel, row, column, pixel map of
+    [B, C, H, W].  For each, sqrt(sum err^2 / sum ref^2) with both sums over all OTHER axes: one figure per slice.
+    Returns {"whole": float, "profiles": {keep: {"err": float64 tensor shaped like the kept axes, "worst": float,
+    "index": index tuple of the worst slice, "median": float}}}.  A profile whose slices hold fewer than `min_elems`
+    elements is refused (ValueError): below that the figure is noise, not a property of the kernel."""
+    if ref.dtype != torch.float64:
+        raise TypeError("error_profiles: the reference must be float64")
+    ref = ref.detach().cpu()
+    got = got.detach().double().cpu()
+    if got.shape != ref.shape:
+        raise ValueError(f"error_profiles: shapes differ, {tuple(got.shape)} against {tuple(ref.shape)}")
+    e2, r2 = (got - ref) ** 2, ref ** 2
+    out = {"whole": float((e2.sum() / r2.sum().clamp_min(1e-300)).sqrt()), "profiles": {}}
+    for keep in keeps:
+        keep = tuple(int(a) % ref.dim() for a in keep)
+        if not keep or len(set(keep)) != len(keep) or list(keep) != sorted(keep):
+            raise ValueError(f"error_profiles: kept axes {keep} must be distinct and ascending")
+        n_slices = 1
+        for a in keep:
+            n_slices *= ref.shape[a]
+        per = ref.numel() // max(1, n_slices)
+        if per < min_elems:
+            raise ValueError(f"error_profiles: slices of profile {keep} hold {per} < {min_elems} elements")
+        rest = [a for a in range(ref.dim()) if a not in keep]
+        num = e2.sum(rest) if rest else e2
+        den = r2.sum(rest) if rest else r2
+        err = (num / den).sqrt()                       # a zero-norm slice gives inf / nan: the caller's input is degenerate
+        flat = torch.nan_to_num(err.reshape(-1), nan=float("inf"))
+        i = int(flat.argmax())
+        out["profiles"][keep] = {"err": err, "worst": float(flat[i]), "median": float(flat.median()),
+                                 "index": tuple(int(v) for v in torch.unravel_index(torch.tensor(i), err.shape))}
+    return out
+
+
 def synth_points(N: int, seed: int):
     """Synthetic LiDAR sweep: azimuth U(-pi,pi), elevation U(-30.5,10.5) deg,
     range log-U(0.8,95) m, intensity U(0,255) -> float32 [N,4]."""

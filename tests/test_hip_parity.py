@@ -525,8 +525,16 @@ def test_groupnorm_large_mean(dev):
     x = seeded_randn(1, 64, 32, 1024, seed=12) * 0.01 + 30.0
     ref = D.group_norm(x.double(), 8, None, None, 1e-6)
     y = K.groupnorm(x.to(dev), 8, 1e-6)
-    r_hip, r_torch = rel_l2(y, ref), rel_l2(D.group_norm(x, 8, None, None, 1e-6), ref)
+    ref32 = D.group_norm(x, 8, None, None, 1e-6)
+    r_hip, r_torch = rel_l2(y, ref), rel_l2(ref32, ref)
     assert r_hip < 1e-4, (r_hip, r_torch)  # pivot-shifted sums: only input quantisation left
+    # ... and by (sample, group), row and column: the two conditions of DESIGN.md "Error profiles"
+    from tests._profile_cases import GN_KEEPS, check_profiles, gn_views
+
+    lines, fails = check_profiles(gn_views(y, 8), gn_views(ref32, 8), gn_views(ref, 8), GN_KEEPS, 1e-4,
+                                  name="groupnorm large mean, full width")
+    print("\n".join(lines))
+    assert not fails, fails
 
 
 # ------------------------------------------------------------------------------------- resample
