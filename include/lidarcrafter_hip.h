@@ -851,6 +851,16 @@ int lc_rbf_kernel_sum(const float* p, const float* q, int M, int Mq, int D, floa
  * nearest point of the other set, both directions; first minimum wins. */
 int lc_chamfer3d_fwd(const float* xyz1, const float* xyz2, int B, int N, int M, float* dist1,
                      int32_t* idx1, float* dist2, int32_t* idx2, lc_stream_t s);
+/* Earth Mover's Distance by the auction algorithm, forward (lidargen/metrics/modules/emd/emd_cuda.cu emd_cuda_forward
+ * with the state of emd_module.py:59-70; csrc/emd.hip): xyz1, xyz2 [B,n,3] -> assignment [B,n]
+ * (the object of xyz2 each point of xyz1 holds after `iters` iterations; the last one gives every unassigned point its
+ * own bid, so objects may repeat) and dist [B,n] = |xyz1[j] - xyz2[assignment[j]]|^2.  Any n >= 1 (<= 2^24), B >= 1
+ * (<= 65535), iters >= 1, eps >= 0.  All state lives in `scratch` (lc_emd_scratch_bytes(B, n) bytes, 16-byte aligned)
+ * and is initialised by every call; no host synchronisation.  target_blocks: blocks per pair the bid pass spreads over,
+ * 0 = auto (max(64, 2048 / B)), otherwise 1 ... auto (tests: it moves the thresholds between the pass's splits). */
+int64_t lc_emd_scratch_bytes(int B, int n);
+int lc_emd_fwd(const float* xyz1, const float* xyz2, int B, int n, float eps, int iters, int target_blocks,
+               float* dist, int32_t* assignment, void* scratch, lc_stream_t s);
 
 /* ---------------------------------------------------------------------------------------------
  * Scene-graph layout generator (lidargen/models/unets/unet_1d.py UNet1DModel on a signal of length 1, graph.py

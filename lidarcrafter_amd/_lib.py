@@ -178,6 +178,8 @@ SIGNATURES = {
     "lc_rbf_partials_elems": (i64, [i32, i32]),
     "lc_rbf_kernel_sum": (i32, [vp, vp, i32, i32, i32, f32, vp, vp]),
     "lc_chamfer3d_fwd": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]),
+    "lc_emd_scratch_bytes": (i64, [i32, i32]),
+    "lc_emd_fwd": (i32, [vp, vp, i32, i32, f32, i32, i32, vp, vp, vp, vp]),
     "lc_compact_scratch_elems": (i64, [i32]),
     "lc_compact_points": (i32, [vp, vp, i32, i32, vp, vp, vp, vp, vp]),
     "lc_points_in_boxes_index": (i32, [vp, vp, i32, i32, i32, f32, vp, vp]),

@@ -2571,6 +2571,29 @@ def chamfer3d(xyz1: torch.Tensor, xyz2: torch.Tensor):
     return d1, d2, i1, i2
 
 
+def emd_forward(xyz1: torch.Tensor, xyz2: torch.Tensor, eps: float, iters: int, target_blocks: int = 0):
+    """xyz1, xyz2 [B,n,3] -> (dist [B,n] float32, assignment int32 [B,n]): the auction approximation of the Earth Mover's
+    Distance (emd_module.py:46-76 / emd_cuda.cu emd_cuda_forward); assignment[b,j] is the point of xyz2 that xyz1[b,j] holds
+    after `iters` iterations, dist its squared distance.  target_blocks: see lc_emd_fwd (0 = auto)."""
+    _req(xyz1, "xyz1"), _req(xyz2, "xyz2")
+    if xyz1.dim() != 3 or xyz2.dim() != 3 or xyz1.shape[2] != 3 or tuple(xyz1.shape) != tuple(xyz2.shape):
+        raise ValueError("emd_forward: expected two [B,n,3] clouds of the same shape")
+    B, n, _ = xyz1.shape
+    if B < 1 or n < 1 or int(iters) < 1 or not float(eps) >= 0.0:
+        raise ValueError("emd_forward: needs B >= 1, n >= 1, iters >= 1 and eps >= 0")
+    xyz1, xyz2 = xyz1.contiguous(), xyz2.contiguous()
+    dev = xyz1.device
+    nbytes = int(lib().lc_emd_scratch_bytes(B, n))
+    if nbytes <= 0:
+        raise ValueError("emd_forward: B or n beyond what lc_emd_fwd takes")
+    scratch = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+    dist = torch.empty((B, n), device=dev, dtype=_F32)
+    assignment = torch.empty((B, n), device=dev, dtype=torch.int32)
+    check(lib().lc_emd_fwd(xyz1.data_ptr(), xyz2.data_ptr(), B, n, float(eps), int(iters), int(target_blocks),
+                           dist.data_ptr(), assignment.data_ptr(), scratch.data_ptr(), _stream()), "lc_emd_fwd")
+    return dist, assignment
+
+
 def roiaware_pool3d_forward(rois, pts, pts_feature, out_size, max_pts_each_voxel: int, method: int):
     """-> (pooled [N,X,Y,Z,C], pts_idx_of_voxels int32 [N,X,Y,Z,max_pts], argmax int32 [N,X,Y,Z,C])."""
     for n_, t_ in (("rois", rois), ("pts", pts), ("pts_feature", pts_feature)):
