@@ -851,6 +851,38 @@ int lc_rbf_kernel_sum(const float* p, const float* q, int M, int Mq, int D, floa
  * nearest point of the other set, both directions; first minimum wins. */
 int lc_chamfer3d_fwd(const float* xyz1, const float* xyz2, int B, int N, int M, float* dist1,
                      int32_t* idx1, float* dist2, int32_t* idx2, lc_stream_t s);
+/* The 2-D variant (lidargen/metrics/modules/chamfer2D/chamfer2D.cu NmDistanceKernel): xyz1 [B,N,2], xyz2 [B,M,2];
+ * d = dx*dx + dy*dy with separate float32 roundings, first minimum wins.  B <= 65535 (LC_EUNSUP otherwise). */
+int lc_chamfer2d_fwd(const float* xyz1, const float* xyz2, int B, int N, int M, float* dist1,
+                     int32_t* idx1, float* dist2, int32_t* idx2, lc_stream_t s);
+/* Chamfer distance of BEV cell sets on their nx x ny grid (csrc/bev_chamfer.hip).
+ * lc_bev_grid_supported: LC_OK when the distance transform takes the grid; LC_EINVAL for a non-positive size; LC_EUNSUP
+ *   when 2 nx^2 ny^2 >= 2^32 (the u32 distances would overflow) or a 64-column strip of it does not fit 64 KiB of LDS.
+ * lc_bev_occupancy_bits: clouds (float32 points `pt_stride` floats apart, x / y first; cloud c is points offsets[c] ..
+ *   offsets[c+1], max_points the longest) -> bits [n_clouds][nx][ceil(ny/32)] (bit iy & 31 of word iy >> 5 of row ix; mask
+ *   and floor of lc_bev_occupancy_accumulate) and counts[c], the number of cells of cloud c.  Any grid.
+ * lc_bev_cell_lists: cells[cell_offsets[c] .. cell_offsets[c+1]) = ix * ny + iy of the set bits of cloud c, ascending;
+ *   cell_offsets is the exclusive prefix sum of counts.
+ * lc_bev_distance_transform: Dt[cell * ld + m] = min over the cells c' of bitmap m of (di^2 ny^2 + dj^2 nx^2), 0xFFFFFFFF
+ *   for an empty bitmap; columns n_maps .. ld are zeroed.  tmp: n_maps * nx * ny words.  n_maps <= 65535.
+ * lc_bev_pair_sums: A[i * nJ + j] = sum over the cells of list i (cell_offsets[i] .. cell_offsets[i+1]) of Dt[cell * ld + j].
+ *   nI <= 65535.
+ * lc_bev_chamfer_combine: cd[i][j] = (A_rs[i*nJ+j] / count_r[i] + A_sr[j*nI+i] / count_s[j]) / (2 nx^2 ny^2) in float64;
+ *   matrix (may be NULL) [i * matrix_ld + j0 + j] = cd; the row minimum and j0 + its first arg-minimum replace
+ *   min_out[i] / argmin_out[i] when `first` or when the minimum is smaller (chunks in ascending j0: first index wins). */
+int lc_bev_grid_supported(int nx, int ny);
+int lc_bev_occupancy_bits(const float* pts, int pt_stride, const int64_t* offsets, int n_clouds, int64_t max_points,
+                          float x0, float x1, float y0, float y1, float voxel, int min_bound_x, int min_bound_y,
+                          int nx, int ny, uint32_t* bits, int32_t* counts, lc_stream_t s);
+int lc_bev_cell_lists(const uint32_t* bits, int n_clouds, int nx, int ny, const int64_t* cell_offsets,
+                      int32_t* cells, lc_stream_t s);
+int lc_bev_distance_transform(const uint32_t* bits, int n_maps, int nx, int ny, uint32_t* tmp, uint32_t* Dt,
+                              int ld, lc_stream_t s);
+int lc_bev_pair_sums(const int32_t* cells, const int64_t* cell_offsets, int nI, const uint32_t* Dt, int ld,
+                     int nJ, uint64_t* A, lc_stream_t s);
+int lc_bev_chamfer_combine(const uint64_t* A_rs, const uint64_t* A_sr, const int32_t* count_r,
+                           const int32_t* count_s, int nI, int nJ, int64_t j0, int first, int nx, int ny,
+                           double* min_out, int64_t* argmin_out, double* matrix, int64_t matrix_ld, lc_stream_t s);
 /* Earth Mover's Distance by the auction algorithm, forward (lidargen/metrics/modules/emd/emd_cuda.cu emd_cuda_forward
  * with the state of emd_module.py:59-70; csrc/emd.hip): xyz1, xyz2 [B,n,3] -> assignment [B,n]
  * (the object of xyz2 each point of xyz1 holds after `iters` iterations; the last one gives every unassigned point its

@@ -154,7 +154,51 @@ __global__ __launch_bounds__(256) void nn_kernel(const float* __restrict__ q, in
     if (j < n) { dist[(long long)b * n + j] = best; idx[(long long)b * n + j] = best_i; }
 }
 
+// The 2-D variant, lidargen/metrics/modules/chamfer2D/chamfer2D.cu NmDistanceKernel: d = x2*x2 + y2*y2 with x2 = other - own,
+// separate roundings; the first minimum wins inside a chunk of 512 targets (strict <) and an earlier chunk keeps a tie
+// (strict > across chunks).
+__global__ __launch_bounds__(256) void nn2d_kernel(const float* __restrict__ q, int n,
+                                                  const float* __restrict__ t, int m,
+                                                  float* __restrict__ dist, int* __restrict__ idx) {
+    __shared__ float buf[NN_TILE * 2];
+    const int b = blockIdx.y;
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    const float* qb = q + (long long)b * n * 2;
+    const float* tb = t + (long long)b * m * 2;
+    float x1 = 0.f, y1 = 0.f;
+    if (j < n) { x1 = qb[2 * j]; y1 = qb[2 * j + 1]; }
+    float best = 0.f;
+    int best_i = 0;
+    for (int k2 = 0; k2 < m; k2 += NN_TILE) {
+        const int cnt = (m - k2 < NN_TILE ? m - k2 : NN_TILE);
+        __syncthreads();
+        for (int e = threadIdx.x; e < cnt * 2; e += 256) buf[e] = tb[(long long)k2 * 2 + e];
+        __syncthreads();
+        float cb = 0.f;
+        int ci = 0;
+        for (int k = 0; k < cnt; ++k) {
+            const float x2 = buf[2 * k] - x1, y2 = buf[2 * k + 1] - y1;
+            const float d = x2 * x2 + y2 * y2;
+            if (k == 0 || d < cb) { cb = d; ci = k2 + k; }
+        }
+        if (k2 == 0 || best > cb) { best = cb; best_i = ci; }
+    }
+    if (j < n) { dist[(long long)b * n + j] = best; idx[(long long)b * n + j] = best_i; }
+}
+
 }  // namespace
+
+extern "C" int lc_chamfer2d_fwd(const float* xyz1, const float* xyz2, int B, int N, int M, float* dist1,
+                                int32_t* idx1, float* dist2, int32_t* idx2, lc_stream_t s) {
+    if (!xyz1 || !xyz2 || !dist1 || !idx1 || !dist2 || !idx2 || B <= 0 || N <= 0 || M <= 0)
+        return LC_EINVAL;
+    if (B > 65535) return LC_EUNSUP;
+    hipLaunchKernelGGL(nn2d_kernel, dim3((N + 255) / 256, B), dim3(256), 0, lc_s(s), xyz1, N, xyz2, M,
+                       dist1, idx1);
+    hipLaunchKernelGGL(nn2d_kernel, dim3((M + 255) / 256, B), dim3(256), 0, lc_s(s), xyz2, M, xyz1, N,
+                       dist2, idx2);
+    return lc_launch_status();
+}
 
 extern "C" int lc_chamfer3d_fwd(const float* xyz1, const float* xyz2, int B, int N, int M, float* dist1,
                                 int32_t* idx1, float* dist2, int32_t* idx2, lc_stream_t s) {

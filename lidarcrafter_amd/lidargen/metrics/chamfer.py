@@ -1,6 +1,8 @@
 """Chamfer distance -- mirror of the reference's `lidargen/metrics/modules/chamfer3D/
-dist_chamfer_3D.py` (`chamfer_3DDist`) and of `compute_pairwise_cd` / `compute_pairwise_cd_batch`
-(`lidargen/metrics/metric_utils.py:415-444`).  Forward only (evaluation)."""
+dist_chamfer_3D.py` (`chamfer_3DDist`), `modules/chamfer2D/dist_chamfer_2D.py` (`chamfer_2DDist`) and of
+`compute_pairwise_cd` / `compute_pairwise_cd_batch` (`lidargen/metrics/metric_utils.py:415-444`).  Forward only
+(evaluation).  `bev_min_matching` is this project's own: the row minima that compute_mmd averages, on the grid route
+(ops.bev_chamfer_min) or, for a grid that route does not take, on the literal one."""
 from __future__ import annotations
 
 import numpy as np
@@ -13,6 +15,11 @@ from lidarcrafter_amd import ops as K
 class chamfer_3DDist(nn.Module):
     def forward(self, input1, input2):
         return K.chamfer3d(input1.float(), input2.float())
+
+
+class chamfer_2DDist(nn.Module):
+    def forward(self, input1, input2):
+        return K.chamfer2d(input1.float(), input2.float())
 
 
 def _dev(a):
@@ -30,13 +37,48 @@ def compute_pairwise_cd(x, y, module=None):
 
 def compute_pairwise_cd_batch(reference, samples):
     """One reference cloud against a list of clouds: shorter clouds are padded with points at 1e6
-    (as the reference does) and the padded tail is excluded from the means."""
-    assert reference.ndim == 2 and reference.shape[1] == 3, "3-D clouds (the 2-D variant is out of scope)"
+    (as the reference does) and the padded tail is excluded from the means.  [n, 3] clouds go through
+    chamfer_3DDist, [n, 2] clouds (pcd2bev_bin's cells) through chamfer_2DDist."""
+    assert reference.ndim == 2 and reference.shape[1] in (2, 3), "[n, 3] or [n, 2] clouds"
+    dim = reference.shape[1]
+    module = chamfer_3DDist() if dim == 3 else chamfer_2DDist()
+    host = lambda a: a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a
+    reference, samples = host(reference), [host(s) for s in samples]
     len_r, len_s = reference.shape[0], [s.shape[0] for s in samples]
     max_len = max([len_r] + len_s)
-    padv = lambda a: np.vstack([a, np.ones((max_len - a.shape[0], 3), dtype=np.float32) * 1e6])
+    padv = lambda a: np.vstack([a, np.ones((max_len - a.shape[0], dim), dtype=np.float32) * 1e6])
     ref = _dev(padv(np.asarray(reference, np.float32)))
     smp = _dev(np.stack([padv(np.asarray(s, np.float32)) for s in samples]))
-    dist_r, dist_s, _, _ = chamfer_3DDist()(ref[None].expand_as(smp).contiguous(), smp)
+    dist_r, dist_s, _, _ = module(ref[None].expand_as(smp).contiguous(), smp)
     return [((dist_r[i, :len_r].mean() + dist_s[i, :len_s[i]].mean()) / 2.).item()
             for i in range(smp.shape[0])]
+
+
+def bev_min_matching(reference, samples, x_range, y_range, voxel_size=0.5, route="auto"):
+    """For every reference cloud: (min over the samples of the 2-D chamfer distance of their BEV cell sets, its index),
+    two float64 / int64 numpy arrays.  route 'grid': ops.bev_chamfer_min (exact); 'literal': pcd2bev_bin's cells through
+    compute_pairwise_cd_batch per reference, as the reference's compute_mmd does; 'auto': the grid route, the literal
+    one where the grid is outside what the distance transform takes."""
+    from . import metric_utils
+
+    assert route in ("auto", "grid", "literal")
+    ref, smp = [_dev(c).float() for c in reference], [_dev(c).float() for c in samples]
+    if route != "literal":
+        try:
+            mn, arg = K.bev_chamfer_min(ref, smp, x_range, y_range, voxel_size)
+            return mn.cpu().numpy(), arg.cpu().numpy()
+        except K.BevGridUnsupported:
+            if route == "grid":
+                raise
+    r_cells, s_cells = ([c.cpu().numpy() for c in sets]
+                        for sets in metric_utils.bev_bin(x_range, y_range, voxel_size, ref, smp))
+    for name, sets in (("reference", r_cells), ("sample", s_cells)):
+        for k, c in enumerate(sets):
+            if c.shape[0] == 0:
+                raise ValueError(f"bev_min_matching: {name} cloud {k} has no point inside the BEV range")
+    mins, args = [], []
+    for r in r_cells:
+        d = compute_pairwise_cd_batch(r, s_cells)
+        args.append(int(np.argmin(d)))
+        mins.append(d[args[-1]])
+    return np.asarray(mins, np.float64), np.asarray(args, np.int64)

@@ -1,6 +1,7 @@
 """Voxel scatter of the weight-free metrics -- mirror of the reference's
 lidargen/metrics/metric_utils.py: `ravel_hash` :28-40, `sparse_quantize` :43-66, `pcd2bev_sum`
-:233-258 (the BEV occupancy volume the JSD of eval_utils.compute_jsd :84-95 is computed from).
+:233-258 (the BEV occupancy volume the JSD of eval_utils.compute_jsd :84-95 is computed from), `pcd2bev_bin` :261-284
+(the BEV cell sets the MMD of eval_utils.compute_mmd is computed from; one bitmap per cloud, csrc/bev_chamfer.hip).
 The point sets stay on the device: sweeps are scattered with atomics (lc_bev_occupancy_accumulate),
 unique voxels come from a device radix sort (lc_sparse_quantize).  numpy in -> numpy out, CUDA
 tensors in -> CUDA tensors out.  The feature-extractor front-ends of that module (pcd2range,
@@ -70,6 +71,31 @@ def pcd2bev_sum(data_type, *args, voxel_size=VOXEL_SIZE):
         else:
             output += (acc.grid.cpu().numpy() if is_np else acc.grid,)
     return output
+
+
+def bev_bin(x_range, y_range, voxel_size, *args):
+    """pcd2bev_bin on any range: for every list of clouds in `args` a list of float32 [k, 2] arrays, the unique cells
+    (strict mask, floor(xy / voxel) - ceil(min / voxel)) in row-major order with x major, each divided by (nx, ny) in
+    float64 and rounded to float32.  A cloud with no point in range gives a [0, 2] array."""
+    output = tuple()
+    for data in args:
+        data = list(data)
+        if not data:
+            output += ([],)
+            continue
+        devd = [_dev(pcd) for pcd in data]
+        cells, (nx, ny) = K.bev_cells([p for p, _ in devd], x_range, y_range, voxel_size)
+        shape = torch.tensor([nx, ny], dtype=torch.float64, device=cells[0].device)
+        vals = [(c.to(torch.float64) / shape).to(torch.float32) for c in cells]
+        output += ([v.cpu().numpy() if is_np else v for v, (_, is_np) in zip(vals, devd)],)
+    return output
+
+
+def pcd2bev_bin(data_type, *args, voxel_size=0.5):
+    """For every set of sweeps in `args`: per sweep the float32 [k, 2] unique BEV cells of `data_type`'s range, as
+    cell / (nx, ny) (metric_utils.py:261-284)."""
+    cfg = DATA_CONFIG[data_type]
+    return bev_bin(cfg["x"], cfg["y"], voxel_size, *args)
 
 
 def compute_jsd(reference, samples, data):

@@ -2571,6 +2571,174 @@ def chamfer3d(xyz1: torch.Tensor, xyz2: torch.Tensor):
     return d1, d2, i1, i2
 
 
+def chamfer2d(xyz1: torch.Tensor, xyz2: torch.Tensor):
+    """xyz1 [B,N,2], xyz2 [B,M,2] -> (dist1 [B,N], dist2 [B,M], idx1 int32 [B,N], idx2 int32 [B,M]): the 2-D variant
+    (dist_chamfer_2D.py / chamfer2D.cu), float32 arithmetic of the reference kernel, first minimum wins."""
+    _req(xyz1, "xyz1"), _req(xyz2, "xyz2")
+    if xyz1.dim() != 3 or xyz2.dim() != 3 or xyz1.shape[2] != 2 or xyz2.shape[2] != 2 or \
+            xyz1.shape[0] != xyz2.shape[0]:
+        raise ValueError("chamfer2d: expected [B,N,2] and [B,M,2]")
+    xyz1, xyz2 = xyz1.contiguous(), xyz2.contiguous()
+    B, N, _ = xyz1.shape
+    M = xyz2.shape[1]
+    dev = xyz1.device
+    d1 = torch.empty((B, N), device=dev, dtype=_F32)
+    d2 = torch.empty((B, M), device=dev, dtype=_F32)
+    i1 = torch.empty((B, N), device=dev, dtype=torch.int32)
+    i2 = torch.empty((B, M), device=dev, dtype=torch.int32)
+    check(lib().lc_chamfer2d_fwd(xyz1.data_ptr(), xyz2.data_ptr(), B, N, M, d1.data_ptr(),
+                                 i1.data_ptr(), d2.data_ptr(), i2.data_ptr(), _stream()),
+          "lc_chamfer2d_fwd")
+    return d1, d2, i1, i2
+
+
+class BevGridUnsupported(ValueError):
+    """The grid is outside what the distance-transform route takes (lc_bev_grid_supported): callers fall back to the
+    literal chamfer_2DDist route."""
+
+
+def _bev_grid(x_range, y_range, voxel):
+    import math
+
+    voxel = float(voxel)
+    if not voxel > 0.0:
+        raise ValueError("voxel size must be positive")
+    nx = math.ceil((x_range[1] - x_range[0]) / voxel)
+    ny = math.ceil((y_range[1] - y_range[0]) / voxel)
+    if nx <= 0 or ny <= 0:
+        raise ValueError("empty BEV range")
+    return nx, ny, (math.ceil(x_range[0] / voxel), math.ceil(y_range[0] / voxel))
+
+
+def _bev_bits(clouds, x_range, y_range, voxel, what):
+    """Clouds (a list of [N, >=2] float32 CUDA tensors, ragged) -> (bits int32 [n, nx * ceil(ny/32)], counts int32 [n])."""
+    clouds = list(clouds)
+    if not clouds:
+        raise ValueError(f"{what}: no clouds")
+    for k, c in enumerate(clouds):
+        _req(c, f"{what}[{k}]")
+        if c.dim() != 2 or c.shape[1] < 2:
+            raise ValueError(f"{what}[{k}]: expected an [N, >=2] cloud")
+    nx, ny, mb = _bev_grid(x_range, y_range, voxel)
+    dev = clouds[0].device
+    width = clouds[0].shape[1]
+    if len(clouds) == 1:
+        pts = clouds[0].contiguous()
+    elif all(c.shape[1] == width for c in clouds):
+        pts = torch.cat(clouds)
+    else:
+        pts, width = torch.cat([c[:, :2] for c in clouds]), 2
+    lens = [c.shape[0] for c in clouds]
+    offs = torch.zeros(len(clouds) + 1, dtype=torch.int64)
+    offs[1:] = torch.cumsum(torch.tensor(lens, dtype=torch.int64), 0)
+    offs = offs.to(dev)
+    n, W = len(clouds), nx * ((ny + 31) // 32)
+    bits = torch.empty((n, W), device=dev, dtype=torch.int32)
+    counts = torch.empty(n, device=dev, dtype=torch.int32)
+    with torch.cuda.device(dev):
+        check(lib().lc_bev_occupancy_bits(pts.data_ptr() if pts.numel() else None, width, offs.data_ptr(), n, max(lens),
+                                          float(x_range[0]), float(x_range[1]), float(y_range[0]), float(y_range[1]),
+                                          float(voxel), mb[0], mb[1], nx, ny, bits.data_ptr(), counts.data_ptr(),
+                                          _stream()), "lc_bev_occupancy_bits")
+    return bits, counts, (nx, ny)
+
+
+def _bev_cell_lists(bits, counts, nx, ny):
+    """-> (cells int32 [total], offsets int64 [n + 1] on the device, counts as a host list)."""
+    dev, n = bits.device, bits.shape[0]
+    offs = torch.zeros(n + 1, device=dev, dtype=torch.int64)
+    offs[1:] = torch.cumsum(counts, 0)
+    host = counts.tolist()
+    cells = torch.empty(max(sum(host), 1), device=dev, dtype=torch.int32)
+    with torch.cuda.device(dev):
+        check(lib().lc_bev_cell_lists(bits.data_ptr(), n, nx, ny, offs.data_ptr(), cells.data_ptr(), _stream()),
+              "lc_bev_cell_lists")
+    return cells, offs, host
+
+
+def bev_cells(clouds, x_range, y_range, voxel):
+    """Per cloud the unique cells of the BEV grid it touches, int32 [k, 2] (ix, iy) in row-major order with x major
+    (np.unique order of the reference's ravel_hash); k = 0 for a cloud with no point strictly inside the range."""
+    bits, counts, (nx, ny) = _bev_bits(clouds, x_range, y_range, voxel, "clouds")
+    cells, _, host = _bev_cell_lists(bits, counts, nx, ny)
+    ij = torch.stack([cells // ny, cells % ny], dim=1)
+    out, at = [], 0
+    for k in host:
+        out.append(ij[at:at + k])
+        at += k
+    return out, (nx, ny)
+
+
+def bev_chamfer_min(ref_clouds, sample_clouds, x_range, y_range, voxel, *, return_matrix: bool = False,
+                    max_scratch_bytes: int = 256 << 20):
+    """For every reference cloud the smallest 2-D chamfer distance to a sample cloud, on the BEV cell sets of
+    pcd2bev_bin (cells / (nx, ny)), in exact integer arithmetic up to the final float64 division (csrc/bev_chamfer.hip).
+    -> (min float64 [R], argmin int64 [R][, matrix float64 [R, S] when return_matrix]).  The distance transforms of a
+    chunk of references and of samples live in scratch of at most about `max_scratch_bytes`; the R x S matrix exists
+    only when asked for.  Raises BevGridUnsupported for a grid the transform does not take and ValueError naming a
+    cloud that has no cell in range."""
+    ref_clouds, sample_clouds = list(ref_clouds), list(sample_clouds)
+    nx, ny, _ = _bev_grid(x_range, y_range, voxel)
+    if lib().lc_bev_grid_supported(nx, ny) != 0:
+        for k, c in enumerate(ref_clouds + sample_clouds):
+            _req(c, f"clouds[{k}]")
+        raise BevGridUnsupported(f"bev_chamfer_min: a {nx} x {ny} grid is outside the distance-transform route")
+    R, S = len(ref_clouds), len(sample_clouds)
+    bits, counts, _ = _bev_bits(ref_clouds + sample_clouds, x_range, y_range, voxel, "clouds")
+    cells, offs, host = _bev_cell_lists(bits, counts, nx, ny)
+    for k, c in enumerate(host):
+        if c == 0:
+            which = f"reference cloud {k}" if k < R else f"sample cloud {k - R}"
+            raise ValueError(f"bev_chamfer_min: {which} has no point inside the BEV range")
+    dev, ncell = bits.device, nx * ny
+    # a chunk of n references against n samples: two transposed transforms and the transform in flight (12 ncell n bytes)
+    # and two n x n sums (16 n^2 bytes); the largest n under the cap, at least 1
+    import math
+
+    n = (math.isqrt((12 * ncell) ** 2 + 64 * max(int(max_scratch_bytes), 0)) - 12 * ncell) // 32
+    n = min(max(n, 1), 32768)
+    rc, sc = min(n, R), min(n, S)
+    tmp = torch.empty(max(rc, sc) * ncell, device=dev, dtype=torch.int32)
+    dt_r = torch.empty(ncell * _pad16(rc), device=dev, dtype=torch.int32)
+    dt_s = torch.empty(ncell * _pad16(sc), device=dev, dtype=torch.int32)
+    a_rs = torch.empty(rc * sc, device=dev, dtype=torch.int64)
+    a_sr = torch.empty(rc * sc, device=dev, dtype=torch.int64)
+    minv = torch.empty(R, device=dev, dtype=torch.float64)
+    argmin = torch.empty(R, device=dev, dtype=torch.int64)
+    matrix = torch.empty((R, S), device=dev, dtype=torch.float64) if return_matrix else None
+    L, st = lib(), None
+
+    def transform(first, count, out):
+        check(L.lc_bev_distance_transform(bits[first].data_ptr(), count, nx, ny, tmp.data_ptr(), out.data_ptr(),
+                                          _pad16(count), st), "lc_bev_distance_transform")
+
+    with torch.cuda.device(dev):
+        st = _stream()
+        s_done = None
+        for i0 in range(0, R, rc):
+            ni = min(rc, R - i0)
+            transform(i0, ni, dt_r)
+            for j0 in range(0, S, sc):
+                nj = min(sc, S - j0)
+                if s_done != j0:
+                    transform(R + j0, nj, dt_s)
+                    s_done = j0
+                check(L.lc_bev_pair_sums(cells.data_ptr(), offs[i0:].data_ptr(), ni, dt_s.data_ptr(), _pad16(nj), nj,
+                                         a_rs.data_ptr(), st), "lc_bev_pair_sums")
+                check(L.lc_bev_pair_sums(cells.data_ptr(), offs[R + j0:].data_ptr(), nj, dt_r.data_ptr(), _pad16(ni), ni,
+                                         a_sr.data_ptr(), st), "lc_bev_pair_sums")
+                check(L.lc_bev_chamfer_combine(a_rs.data_ptr(), a_sr.data_ptr(), counts[i0:].data_ptr(),
+                                               counts[R + j0:].data_ptr(), ni, nj, j0, int(j0 == 0), nx, ny,
+                                               minv[i0:].data_ptr(), argmin[i0:].data_ptr(),
+                                               matrix[i0:].data_ptr() if return_matrix else None, S, st),
+                      "lc_bev_chamfer_combine")
+    return (minv, argmin, matrix) if return_matrix else (minv, argmin)
+
+
+def _pad16(n: int) -> int:
+    return (n + 15) // 16 * 16
+
+
 def emd_forward(xyz1: torch.Tensor, xyz2: torch.Tensor, eps: float, iters: int, target_blocks: int = 0):
     """xyz1, xyz2 [B,n,3] -> (dist [B,n] float32, assignment int32 [B,n]): the auction approximation of the Earth Mover's
     Distance (emd_module.py:46-76 / emd_cuda.cu emd_cuda_forward); assignment[b,j] is the point of xyz2 that xyz1[b,j] holds
