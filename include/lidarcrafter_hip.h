@@ -752,7 +752,8 @@ int lc_points_in_boxes_index(const float* boxes, const float* pts, int B, int n_
  *   sample_and_save_cond.py:119-124.  ray_angles [1,2,H,W] (elevation, azimuth) radians.
  * lc_condition_preprocess: condition_mask [B,2,H,W] (class id, metric depth) -> out
  *   [B,num_classes+1,H,W] = one_hot(class) ++ LiDARUtility.convert_depth(depth)
- *   (sample_and_save_cond.py:106-117, utils/lidar.py:84-107).
+ *   (sample_and_save_cond.py:106-117, utils/lidar.py:84-107).  The class id is truncated like .long(); an id outside
+ *   [0, num_classes), which F.one_hot rejects, gives an all-zero one-hot.
  * depth_format: 0 log_depth, 1 inverse_depth, 2 depth.
  * ------------------------------------------------------------------------------------------- */
 int lc_range_postprocess(const float* sample, int64_t sample_bs, const float* ray_angles,
