@@ -21,7 +21,7 @@ static inline int lc_launch_status() {
 // convolution epilogues (conv_f16x2_common.h epi_store / LC_DEF_AUX): lines left dirty in the per-XCD L2s are written back at
 // the kernel boundary, in front of the next launch; written through, they stream out while the kernel runs.  Clean same-box
 // A/B of these conversions together (r05z20): C2 262.2 -> 262.7 steps/s, C3 8.90 -> 8.88 ms -- marginal.  The pre-split
-// GroupNorm apply pass is NOT written through (norm.hip LC_GNS_STORE: the pass alone 20.3 -> 29.4 us, the step 3-4 % slower).
+// GroupNorm apply pass is NOT written through (round 5: the pass alone 20.3 -> 29.4 us, the step 3-4 % slower).
 // A first reading of that experiment said "+5 % on the step": the library that measured it wrote its 128-bit planes with
 // inline-assembly stores that lacked the ISA's wait states, the planes were partly garbage (55 of 136 pre-split parity tests
 // failed once they were run against it), and the power-limited convolutions run faster on degenerate operands

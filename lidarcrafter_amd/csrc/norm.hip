@@ -409,13 +409,14 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(
 // OS: 0 = statistics-pass partials; 1 = producer entries, groups of whole channel octets (the block folds ONE group);
 // 2 = producer entries, 2 or 4 channels per group (GroupNorm32 at 64 / 128 channels, round 5): the octet holds 4 / 2
 // groups, wave w of the block folds group w.
-// Store form of the hi / lo planes: 0 = plain (write-back) stores -- shipped; 2 = write-through (sc1) buffer stores.  Round 5
-// measured 2 and four more write-through forms (inline assembly with v_nop / s_nop wait states, four pixels then eight stores
-// back to back, nontemporal): every correct one costs the pass +9 us at 8 x 128 x 16 x 512 and the C2 step 3-5 %
-// (profiles/r05_level0.txt section 8).
-#ifndef LC_GNS_STORE
-#define LC_GNS_STORE 0
-#endif
+// Lane = pixel throughout: a thread owns four pixels 256 apart, 8 dword loads per pixel (a wave instruction reads 256 bytes
+// contiguous per channel), and a wave store instruction covers 1 KiB contiguous of a plane (lane l -> unit base + l: eight
+// whole 128-byte lines).  The first version gave a thread four CONSECUTIVE pixels (8 x 16-byte loads): its stores put lane
+// l at byte 64 l + 16 q, 32 lines of 32 bytes per instruction, and the pass ran 25 % longer at 8 x 128 x 16 x 512
+// (profiles/gn_split_stores.txt; also there: the same loads with the units turned through LDS in front of the stores).
+// No alignment is asked of x, HW or the slab.
+// The plane stores are plain write-back stores: round 5 measured write-through (sc1) forms of them, every correct one
+// +9 us per pass at 8 x 128 x 16 x 512 and 3-5 % on the C2 step (profiles/r05_level0.txt section 8).
 template <int OS>
 __global__ __launch_bounds__(256) void gn_apply_split_kernel(
     const float* __restrict__ x, long long x_bs, const double* __restrict__ part, OctStats2 os,
@@ -425,31 +426,35 @@ __global__ __launch_bounds__(256) void gn_apply_split_kernel(
     __shared__ double sh[12];
     const int oct = blockIdx.y, b = blockIdx.z;
     const int c0 = oct * 8, cpg = C / G, g = c0 / cpg;
-    // The first 8 x 16-byte loads of this thread go out BEFORE the statistics fold (round 5): they do not depend on
+    // The first 4 x 8 loads of this thread go out BEFORE the statistics fold (round 5): they do not depend on
     // it, and the fold (entry loads, fp64 shuffles, one barrier: ~1.5 us) otherwise sits in front of every block's
     // first HBM access -- 30 launches of this kernel per C2 step.
     const float* xp = x + b * x_bs + (long long)c0 * HW;
     const long long per = (HW + gridDim.x - 1) / gridDim.x;
     const long long lo = blockIdx.x * per;
     const long long hi = lo + per < HW ? lo + per : HW;
-    const bool vec = (HW & 3) == 0 && (per & 3) == 0 && (reinterpret_cast<uintptr_t>(xp) & 15) == 0;
-    f32x4 c4_first[8];
+    // pix[k][i]: channel k of pixel p + 256 i.  A group of 256 pixels that starts past the slab's end is skipped by the whole
+    // block (a scalar branch: at 8 x 256 x 8 x 256 and below a slab is 512 pixels, and the two idle groups cost 0.4-0.7 us
+    // per pass when they were loaded and normalised for nothing); inside the last group the loads are unconditional (a
+    // predicated load is an exec-mask branch, and hipcc's waits across branches are vmcnt(0)): a thread past the slab's end
+    // reads the slab's last pixel again and stores nothing.
+    auto load4 = [&](f32x4 (&pix)[8], long long p) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            if (p - threadIdx.x + 256 * i < hi) {
+                const long long pi = p + 256 * i < hi - 1 ? p + 256 * i : hi - 1;
+#pragma unroll
+                for (int k = 0; k < 8; ++k) pix[k][i] = xp[(long long)k * HW + pi];
+            } else {
+#pragma unroll
+                for (int k = 0; k < 8; ++k) pix[k][i] = 0.0f;
+            }
+        }
+    };
+    f32x4 pix_first[8];
     auto issue_first = [&]() {      // (behind the fold's own entry loads: VMEM returns in order, the fold must not wait for x)
         asm volatile("" ::: "memory");
-        // unconditional loads (a predicated load is an exec-mask branch, and hipcc's waits across branches are vmcnt(0)):
-        // a thread without a first quad re-reads the slab's last quad and never uses it (C % 16 == 0: 16 channels x HW
-        // floats behind x always hold 16 bytes)
-        // Only the vector path consumes them.  Off it (HW % 4 != 0 or a slab / pointer that is not 16-byte aligned) a typed
-        // 16-byte load from xp would be misaligned: every thread then reads the 16-byte aligned word at or below x instead
-        // (inside x's allocation: allocation bases are 16-byte aligned) -- still no branch, and nothing is read for nothing
-        // beyond that one cached line.
-        long long p0 = lo + threadIdx.x * 4;
-        p0 = p0 < hi - 4 ? p0 : hi - 4;
-        const float* x_al = reinterpret_cast<const float*>(reinterpret_cast<uintptr_t>(x) & ~static_cast<uintptr_t>(15));
-        const float* src = vec ? xp + (p0 > 0 ? p0 : 0) : x_al;
-        const long long cs = vec ? HW : 0;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) c4_first[k] = *reinterpret_cast<const f32x4*>(src + (long long)k * cs);
+        load4(pix_first, lo + threadIdx.x);
         asm volatile("" ::: "memory");
     };
     // per-channel (mean, rstd): one group per octet when the groups are whole octets; otherwise
@@ -604,48 +609,25 @@ __global__ __launch_bounds__(256) void gn_apply_split_kernel(
             h8[k] = ph.x; h8[k + 1] = ph.y; l8[k] = pl.x; l8[k + 1] = pl.y;
         }
     };
-    if (vec) {
-        // four consecutive pixels per thread: 8 float4 channel loads, 2 x 4 contiguous 16-byte stores; the first quad is
-        // the one issued ahead of the fold (peeled: a select per load inside the loop compiled to 8 branches)
-        const __amdgpu_buffer_rsrc_t rs_yh = lc_wt_buf(yh);
-        const unsigned lo_off = (unsigned)((long long)C8 * HW * 16);          // the lo plane behind the hi plane (< 4 GiB: host check)
-        (void)rs_yh; (void)lo_off;
-        auto quad = [&](const f32x4 (&c4)[8], long long p) {
+    // (the first four pixels are the ones issued ahead of the fold)
+    auto four = [&](const f32x4 (&pix)[8], long long p) {
 #pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                float v[8];
-#pragma unroll
-                for (int k = 0; k < 8; ++k) v[k] = c4[k][q];
-                half8_t h8, l8;
-                one(v, h8, l8);
-#if LC_GNS_STORE == 2      // write-through (sc1) buffer stores: developer A/B (profiles/r05_level0.txt section 8)
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(lc_u32x4, h8), rs_yh, (unsigned)(p + q) * 16u, 0, 16);
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(lc_u32x4, l8), rs_yh,
-                                                       (unsigned)(p + q) * 16u + lo_off, 0, 16);
-#else                      // write-back: shipped
-                yh[p + q] = h8;
-                yl[p + q] = l8;
-#endif
-            }
-        };
-        long long p = lo + threadIdx.x * 4;
-        if (p < hi) quad(c4_first, p);
-        for (p += 1024; p < hi; p += 1024) {
-            f32x4 c4[8];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) c4[k] = *reinterpret_cast<const f32x4*>(xp + (long long)k * HW + p);
-            quad(c4, p);
-        }
-    } else {
-        for (long long p = lo + threadIdx.x; p < hi; p += 256) {
+        for (int i = 0; i < 4; ++i) {
+            if (p - threadIdx.x + 256 * i >= hi) continue;
             float v[8];
 #pragma unroll
-            for (int k = 0; k < 8; ++k) v[k] = xp[(long long)k * HW + p];
+            for (int k = 0; k < 8; ++k) v[k] = pix[k][i];
             half8_t h8, l8;
             one(v, h8, l8);
-            yh[p] = h8;
-            yl[p] = l8;
+            if (p + 256 * i < hi) { yh[p + 256 * i] = h8; yl[p + 256 * i] = l8; }
         }
+    };
+    long long p = lo + threadIdx.x;
+    if (lo < hi) four(pix_first, p);
+    for (p += 1024; p - threadIdx.x < hi; p += 1024) {
+        f32x4 pix[8];
+        load4(pix, p);
+        four(pix, p);
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) am = fmaxf(am, __shfl_xor(am, o, 64));

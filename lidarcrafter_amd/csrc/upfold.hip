@@ -25,6 +25,8 @@ typedef float float2_t __attribute__((ext_vector_type(2)));
 
 // ---- fp32 [B][C][HW] -> ysp[b][plane][c/8][p][8] (the layout of lc_groupnorm_apply*_split), split rule of conv_f16x2.hip:
 // s = x * x_scale, hi = 11 significant bits truncated (packed toward zero), lo = fp16(s - hi); max |s| -> the range record.
+// Lane = pixel, as norm.hip's gn_apply_split_kernel: a thread owns four pixels 256 apart (32 dword loads in flight) and a wave
+// store instruction covers 1 KiB contiguous of a plane.
 __global__ __launch_bounds__(256) void split_plain_kernel(const float* __restrict__ x, long long x_bs,
                                                          half8_t* __restrict__ ysp, long long ysp_bs, int C,
                                                          long long HW, lc_conv_range* range) {
@@ -35,16 +37,21 @@ __global__ __launch_bounds__(256) void split_plain_kernel(const float* __restric
     half8_t* yh = ysp + b * ysp_bs + (long long)oct * HW;
     half8_t* yl = yh + (long long)(C >> 3) * HW;
     float am = 0.0f;
-    for (long long p = (blockIdx.x * 256ll + threadIdx.x) * 4; p < HW; p += (long long)gridDim.x * 1024) {
-        f32x4 c4[8];
+    for (long long tb = blockIdx.x * 1024ll; tb < HW; tb += (long long)gridDim.x * 1024) {
+        const long long p = tb + threadIdx.x;
+        f32x4 pix[8];               // pix[k][i]: channel k of pixel p + 256 i; past the plane's end its last pixel again, not stored
 #pragma unroll
-        for (int k = 0; k < 8; ++k) c4[k] = *reinterpret_cast<const f32x4*>(xp + (long long)k * HW + p);
+        for (int i = 0; i < 4; ++i) {
+            const long long pi = p + 256 * i < HW - 1 ? p + 256 * i : HW - 1;
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
+            for (int k = 0; k < 8; ++k) pix[k][i] = xp[(long long)k * HW + pi];
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
             half8_t h8, l8;
 #pragma unroll
             for (int k = 0; k < 8; k += 2) {
-                const float s0 = c4[k][q] * xs, s1 = c4[k + 1][q] * xs;
+                const float s0 = pix[k][i] * xs, s1 = pix[k + 1][i] * xs;
                 am = fmaxf(am, fmaxf(fabsf(s0), fabsf(s1)));
                 const float h0 = __uint_as_float(__float_as_uint(s0) & 0xFFFFE000u);
                 const float h1 = __uint_as_float(__float_as_uint(s1) & 0xFFFFE000u);
@@ -53,8 +60,7 @@ __global__ __launch_bounds__(256) void split_plain_kernel(const float* __restric
                 const half2_t pl = __builtin_convertvector(r, half2_t);
                 h8[k] = ph.x; h8[k + 1] = ph.y; l8[k] = pl.x; l8[k + 1] = pl.y;
             }
-            yh[p + q] = h8;
-            yl[p + q] = l8;
+            if (p + 256 * i < HW) { yh[p + 256 * i] = h8; yl[p + 256 * i] = l8; }
         }
     }
 #pragma unroll
