@@ -935,6 +935,21 @@ int lc_graph_pool_fwd(const float* t, int64_t t_ld, int s_col, int o_col, const 
                       float* y, int64_t y_ld, int O, int H, lc_stream_t s);
 int lc_time_embed_fwd(const float* t, const float* freqs, float* y, int U, int half, lc_stream_t s);
 
+/* ---------------------------------------------------------------------------------------------
+ * Fused PointNet trunk (lidargen/metrics/extractor/pointnet.py: the per-point MLP 3 -> 64 -> 128 -> 1024 and the max
+ * over the points of STN3d and PointNetfeat; csrc/pointnet.hip).  BatchNorm is folded into
+ * (w, b) by the caller, its scale included (a negative scale does not commute with the max).
+ *   x [B,3,N] channel-major, clouds x_bs floats apart; trans [B,9] row-major 3x3 or NULL: p' = p^T trans[b];
+ *   h1 = relu(w1 p' + b1), h2 = relu(w2 h1 + b2), y[b,c] = max over the N points of (w3 h2 + b3)[c], ReLU on y when
+ *   relu3; w1 [64,3], w2 [128,64], w3 [1024,128] row-major (w2, w3 16-byte aligned), rows of y y_bs floats apart.
+ * Exact fp32 (f32-input MFMA).  Every point counts, (0,0,0) too.  Finite inputs (a NaN activation is dropped by the max,
+ * not propagated).  scratch: lc_pointnet_trunk_scratch_elems(B, N) floats, every word read is written by the same call.
+ * No atomics; a cloud's result does not depend on the batch it is in.  B <= 65535, N < 2^24. */
+int64_t lc_pointnet_trunk_scratch_elems(int B, int N);
+int lc_pointnet_trunk_fwd(const float* x, int64_t x_bs, const float* trans, const float* w1, const float* b1,
+                          const float* w2, const float* b2, const float* w3, const float* b3, int relu3, float* y,
+                          int64_t y_bs, int B, int N, float* scratch, lc_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

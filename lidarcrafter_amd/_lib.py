@@ -196,6 +196,8 @@ SIGNATURES = {
     "lc_rowprep_fwd": (i32, [_rs, i32, vp, i64, i32, i32, i32, f32, vp, vp, i32, vp]),
     "lc_graph_pool_fwd": (i32, [vp, i64, i32, i32, vp, vp, vp, i64, i32, i32, vp]),
     "lc_time_embed_fwd": (i32, [vp, vp, vp, i32, i32, vp]),
+    "lc_pointnet_trunk_scratch_elems": (i64, [i32, i32]),
+    "lc_pointnet_trunk_fwd": (i32, [vp, i64, vp, vp, vp, vp, vp, vp, vp, i32, vp, i64, i32, i32, vp, vp]),
 }
 
 _lib = None

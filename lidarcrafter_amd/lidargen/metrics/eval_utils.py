@@ -2,11 +2,18 @@
 metrics, data)` and the weight-free scores behind it (`compute_cd` :40-51, `compute_emd` :54-65, `compute_mmd` :68-82,
 `compute_jsd` :85-95).  Every score is printed through the reference's OUTPUT_TEMPLATE and also returned; `evaluate`
 returns {metric: score}.  The perceptual metrics (FRID / FSVD / FPVD: pretrained extractors) are not built here and raise;
-`evaluate` also still refuses 'mmd' (its callers rely on that): call `compute_mmd` directly."""
+`evaluate` also still refuses 'mmd' (its callers rely on that): call `compute_mmd` directly.
+
+`extract_point_features` / `compute_fpd` are the Frechet Point Distance of the reference's own evaluator
+(tools/evaluation/evaluate_our.py `EvaluationEngine`: PointNet1 features of every cloud, `distribution.
+compute_frechet_distance` on the two feature sets); `evaluate` does not dispatch them."""
 from __future__ import annotations
 
+import numpy as np
+import torch
+
 from . import OUTPUT_TEMPLATE
-from . import metric_utils
+from . import distribution, metric_utils
 from .chamfer import bev_min_matching, compute_pairwise_cd
 from .emd import compute_pairwise_emd_batch
 
@@ -72,4 +79,55 @@ def compute_jsd(reference, samples, data):
     print("Evaluating (JSD) ...")
     score = metric_utils.compute_jsd(reference, samples, data)
     print(OUTPUT_TEMPLATE.format("JSD ", score))
+    return score
+
+
+def _cloud_cm(a, scale):
+    """[N,3] array or tensor -> CUDA float32 [3,N] scaled (the evaluator's `xyz / DATASET_MAX_DEPTH`, channel-major)."""
+    if isinstance(a, np.ndarray):
+        if not torch.cuda.is_available():
+            raise RuntimeError("extract_point_features needs the MI355X: no CPU fallback on the hot path")
+        a = torch.from_numpy(np.ascontiguousarray(a, np.float32)).cuda()
+    elif not isinstance(a, torch.Tensor) or not a.is_cuda:
+        raise RuntimeError("extract_point_features: tensors must be CUDA(HIP) tensors -- no CPU fallback on the hot path")
+    if a.dim() != 2 or a.shape[1] != 3 or a.shape[0] < 1:
+        raise ValueError(f"extract_point_features: a cloud must be [N, 3] with N >= 1, got {tuple(a.shape)}")
+    return (a.float() * scale).t()
+
+
+def extract_point_features(model, clouds, batch_size=16, scale=1 / 80.0):
+    """Features of `model` (extractor.PointNet1, eval mode, on the GPU) for a list of [N,3] clouds -> [n, width] float64
+    numpy array in input order.  Clouds of one length go through the model together, `batch_size` at a time; `scale`
+    multiplies the coordinates first."""
+    clouds = list(clouds)
+    by_len = {}
+    for i, c in enumerate(clouds):
+        by_len.setdefault(int(c.shape[0]), []).append(i)
+    rows = [None] * len(clouds)
+    for idx in by_len.values():
+        for lo in range(0, len(idx), batch_size):
+            part = idx[lo:lo + batch_size]
+            x = torch.stack([_cloud_cm(clouds[i], scale) for i in part]).contiguous()
+            f = model(x).double().cpu().numpy()
+            for row, i in enumerate(part):
+                rows[i] = f[row]
+    return np.stack(rows) if rows else np.zeros((0, 0))
+
+
+def _as_features(a, model, batch_size):
+    if isinstance(a, np.ndarray) and a.ndim == 2 and a.shape[1] != 3:
+        return a                                    # already a feature matrix (the evaluator caches the real set's)
+    return extract_point_features(model, a, batch_size)
+
+
+def compute_fpd(reference, samples, model, batch_size=16, columns=None):
+    """Score of Frechet Point Distance (FPD): the Frechet distance of the PointNet features of the two sets.  Either set
+    may be a feature matrix ([n, width] numpy array) instead of a list of clouds.  `columns` (a slice or index array)
+    restricts the distance to those feature columns."""
+    print("Evaluating (FPD) ...")
+    fr, fs = _as_features(reference, model, batch_size), _as_features(samples, model, batch_size)
+    if columns is not None:
+        fr, fs = fr[:, columns], fs[:, columns]
+    score = distribution.compute_frechet_distance(fr, fs)
+    print(OUTPUT_TEMPLATE.format("FPD ", score))
     return score

@@ -266,6 +266,40 @@ def seeded_fill_layout_gen(module: torch.nn.Module, salt: int = 0) -> torch.nn.M
     return module
 
 
+@torch.no_grad()
+def seeded_fill_pointnet(module: torch.nn.Module, salt: int = 0) -> torch.nn.Module:
+    """Seeded weights of the PointNet extractor (STN3d / PointNetfeat / PointNet1), keyed by state_dict name: `seeded_fill`,
+    then what it leaves trivial -- BatchNorm running means at 0.3 r, running variances in [0.5, 1.5], and about a quarter
+    of the entries of every `bn3.weight` (the BatchNorm in front of a max over the points) negative, so a scale applied
+    behind the max instead of inside the product shows."""
+    seeded_fill(module, salt)
+    for key, p in list(module.named_parameters()) + list(module.named_buffers()):
+        g = _gen_for(key, salt + 1)
+        if key.endswith("running_mean"):
+            v = 0.3 * torch.randn(p.shape, generator=g)
+        elif key.endswith("running_var"):
+            v = 0.5 + torch.rand(p.shape, generator=g)
+        elif key.endswith("bn3.weight"):
+            v = torch.where(torch.rand(p.shape, generator=g) < 0.25, -p.detach().cpu().float(), p.detach().cpu().float())
+        else:
+            continue
+        p.copy_(v.to(device=p.device, dtype=p.dtype))
+    return module
+
+
+def pointnet_clouds(B: int, N: int, seed: int) -> torch.Tensor:
+    """[B, 3, N] float32 clouds as the evaluator feeds them (xyz / 80 of a synthetic sweep, channel-major) with every
+    third point zeroed, as a masked range image leaves it."""
+    import numpy as np
+
+    out = np.empty((B, 3, N), np.float32)
+    for b in range(B):
+        pts = synth_points(N, seed * 1000 + b)[:, :3] / np.float32(80.0)
+        pts[b % 3::3] = 0.0
+        out[b] = pts.T
+    return torch.from_numpy(out)
+
+
 LAYOUT_GEN_VOCAB = {
     "object_idx_to_name": ["__scene__", "car", "truck", "construction_vehicle", "bus", "trailer", "motorcycle", "bicycle",
                            "pedestrian"],
