@@ -950,6 +950,47 @@ int lc_pointnet_trunk_fwd(const float* x, int64_t x_bs, const float* trans, cons
                           const float* w2, const float* b2, const float* w3, const float* b3, int relu3, float* y,
                           int64_t y_bs, int B, int N, float* scratch, lc_stream_t s);
 
+/* ---------------------------------------------------------------------------------------------
+ * Sparse 3-D convolution (csrc/spconv.hip): what the MinkUNet of the Frechet Sparse Volume Distance
+ * (lidargen/metrics/models/minkowskinet/model.py) takes from torchsparse 1.4.0.  A sparse tensor at stride s is rows
+ * F [N, C] over coordinates [N, 4] int32 = (x, y, z, batch), spatial entries multiples of s and unique rows.
+ * Limits (LC_EUNSUP beyond them, before any launch): 0 <= x, y, z <= LC_SPCONV_MAX_COORD, 0 <= batch <=
+ * LC_SPCONV_MAX_BATCH, stride <= LC_SPCONV_MAX_STRIDE, rows <= LC_SPCONV_MAX_ROWS.  The coordinates live on the device:
+ * the caller states `max_coord` (the largest spatial entry) and `n_batch`; a row outside the limits all the same is never
+ * inserted and never found.  A query at C + offset outside [0, LC_SPCONV_MAX_COORD] is absent: it never aliases another
+ * batch's voxel and never wraps.
+ *   lc_spconv_hash_build: table (lc_spconv_hash_bytes(N) bytes, 8-byte aligned) <- the rows of coords.
+ *   lc_spconv_map: nbr [M, K] int32 <- for every row of coords [M, 4] the table row at coords + offset_k, -1 when absent;
+ *     `table` built from n_table rows.  kind 0: K = 27, offsets {-stride, 0, stride}^3, k = ix + 3 iy + 9 iz.
+ *     kind 1: K = 8, offsets {0, stride}^3, k = 4 ix + 2 iy + iz (coords coarse at 2 stride, table fine at stride).
+ *     kind 2: K = 8, the transpose of kind 1 (coords fine at stride, table coarse at 2 stride): entry k of a row is the
+ *     coarse row j with coords = coarse[j] + offset_k, one k per row at the most.
+ *   lc_spconv_fwd: y[j, y_col : y_col + Co] = act(sum_k x[nbr[j,k], :] w[k] + b + res[j, :Co]) for j < M; x rows ldx floats
+ *     apart (n_in of them), w [K, Ci, Co], b [Co] or NULL, res rows ldr apart or NULL, y rows ldy apart; relu != 0: ReLU.
+ *     K in {1, 8, 27}; K = 1 with nbr NULL is the dense product x w.  An entry -1 (or outside [0, n_in)) adds zeros and
+ *     reads nothing.  Ci in {4, 16, 32, 48, 64, 96, 128, 192}, Co in {16, 32, 48, 64, 128} (LC_EUNSUP otherwise); ldx, ldr,
+ *     ldy, y_col multiples of 4 and every pointer 16-byte aligned (LC_EUNSUP).  Exact fp32 (f32-input MFMA), no atomics,
+ *     a row's bits depend on its own neighbours only.  y may not overlap x or res.
+ *   lc_spconv_sector_means: out [n_clouds, 16 C] <- per cloud (rows offsets[c] .. offsets[c+1] of f / coords; offsets a
+ *     device int32 [n_clouds + 1]) and depth sector i the mean of the rows with edges[i] <= d < edges[i+1], d = |xyz -
+ *     mean xyz| * voxel in float32, edges a device float [17]; 0 for an empty sector.  C <= 256, n_clouds <= 65535.
+ *     Fixed summation order, no atomics. */
+#define LC_SPCONV_TILE 64
+#define LC_SPCONV_MAX_COORD 262143
+#define LC_SPCONV_MAX_BATCH 510
+#define LC_SPCONV_MAX_STRIDE 65536
+#define LC_SPCONV_MAX_ROWS 67108864
+int64_t lc_spconv_hash_bytes(int N);
+int lc_spconv_hash_build(const int32_t* coords, int N, int max_coord, int n_batch, void* table, int64_t table_bytes,
+                         lc_stream_t s);
+int lc_spconv_map(const int32_t* coords, int M, int kind, int stride, const void* table, int n_table, int32_t* nbr,
+                  lc_stream_t s);
+int lc_spconv_fwd(const float* x, int64_t ldx, const int32_t* nbr, int n_in, const float* w, const float* b,
+                  const float* res, int64_t ldr, float* y, int64_t ldy, int y_col, int M, int Ci, int Co, int K, int relu,
+                  lc_stream_t s);
+int lc_spconv_sector_means(const float* f, int64_t ldf, const int32_t* coords, const int32_t* offsets, int n_clouds,
+                           int C, const float* edges, float voxel, float* out, lc_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

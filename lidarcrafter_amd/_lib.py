@@ -198,6 +198,11 @@ SIGNATURES = {
     "lc_time_embed_fwd": (i32, [vp, vp, vp, i32, i32, vp]),
     "lc_pointnet_trunk_scratch_elems": (i64, [i32, i32]),
     "lc_pointnet_trunk_fwd": (i32, [vp, i64, vp, vp, vp, vp, vp, vp, vp, i32, vp, i64, i32, i32, vp, vp]),
+    "lc_spconv_hash_bytes": (i64, [i32]),
+    "lc_spconv_hash_build": (i32, [vp, i32, i32, i32, vp, i64, vp]),
+    "lc_spconv_map": (i32, [vp, i32, i32, i32, vp, i32, vp, vp]),
+    "lc_spconv_fwd": (i32, [vp, i64, vp, i32, vp, vp, vp, i64, vp, i64, i32, i32, i32, i32, i32, i32, vp]),
+    "lc_spconv_sector_means": (i32, [vp, i64, vp, vp, i32, i32, vp, f32, vp, vp]),
 }
 
 _lib = None

@@ -1,9 +1,55 @@
-"""Evaluation front-end on the device (SURVEY.md section 8f-3 ii): `bev`, `chamfer`, `emd`, `eval_utils.evaluate`, and the
-Frechet Point Distance (`extractor.pointnet`, `distribution`, `eval_utils.compute_fpd`).  The other learned-feature
-metrics of the reference (FRID / FSVD / FPVD: RangeNet, MinkowskiNet, SPVCNN, PTv3 backbones + checkpoints) are out of
-scope."""
+"""Evaluation front-end on the device (SURVEY.md section 8f-3 ii): `bev`, `chamfer`, `emd`, `eval_utils.evaluate`, the
+Frechet Point Distance (`extractor.pointnet`, `distribution`, `eval_utils.compute_fpd`) and the Frechet Sparse Volume
+Distance (`models.minkowskinet`, `metric_utils.compute_logits`, `eval_utils.compute_fsvd`; sparse 3-D convolution in
+csrc/spconv.hip).  The other two learned-feature metrics of the reference (FRID: RangeNet, FPVD: SPVCNN) are not built."""
+import os
+
 # a score line as the reference prints it: a 50-column rule above and below `|<16 blanks>NAME:1.2345E+00<17 blanks>|`
 _RULE = "-" * 50
 OUTPUT_TEMPLATE = f"{_RULE}\n|{'':16}{{}}:{{:.4E}}{'':17}|\n{_RULE}"
 
-from . import bev, chamfer, distribution, emd, eval_utils, extractor  # noqa: E402,F401
+# the reference's settings (lidargen/metrics/__init__.py:23-36)
+DEFAULT_ROOT = "../pretrained_models/evaluation"
+MODAL2BATCHSIZE = {"range": 100, "voxel": 50, "point_voxel": 25}
+VOXEL_SIZE = 0.05
+NUM_SECTORS = 16
+AGG_TYPE = "depth"
+TYPE2DATASET = {"32": "nuscenes", "64": "kitti"}
+MODALITY2MODEL = {"range": "rangenet", "voxel": "minkowskinet", "point_voxel": "spvcnn"}
+DATASET_CONFIG = {"kitti": {"size": [64, 1024], "fov": [3, -25], "depth_range": [1.0, 56.0], "depth_scale": 6},
+                  "nuscenes": {"size": [32, 1024], "fov": [10, -30], "depth_range": [1.0, 45.0]}}
+
+
+def build_model(dataset_name, model_name, device="cpu", root=None):
+    """The pretrained extractor `model_name` of `dataset_name` from <root>/<dataset_name>/<model_name>/{config.yaml,
+    model.ckpt} (root: DEFAULT_ROOT), in eval mode on `device`.  Only 'minkowskinet' is built.  Nothing is fetched: a
+    missing folder or file raises FileNotFoundError naming the path.  Unlike the reference's `strict=False` a model key
+    missing from the checkpoint raises; keys the model does not have are ignored."""
+    import torch
+    import yaml
+
+    if model_name != "minkowskinet":
+        raise NotImplementedError(f"build_model: '{model_name}' is not built (only 'minkowskinet', the extractor of FSVD)")
+    folder = os.path.join(DEFAULT_ROOT if root is None else os.fspath(root), dataset_name, model_name)
+    if not os.path.isdir(folder):
+        raise FileNotFoundError(f"build_model: no pretrained weights folder at {folder} -- place the reference's "
+                                "config.yaml and model.ckpt there or pass root=<path>; this build does not fetch them")
+    paths = [os.path.join(folder, n) for n in ("config.yaml", "model.ckpt")]
+    for p in paths:
+        if not os.path.isfile(p):
+            raise FileNotFoundError(f"build_model: {p} is missing; this build does not fetch it")
+    from .models.minkowskinet.model import Model
+
+    with open(paths[0], "r") as f:
+        model = Model(yaml.safe_load(f))
+    state = torch.load(paths[1], map_location="cpu", weights_only=False)["state_dict"]
+    own = model.state_dict()
+    missing = [k for k in own if k not in state]
+    if missing:
+        raise KeyError(f"build_model: {paths[1]} lacks {len(missing)} keys of the model, the first: {missing[:4]}")
+    model.load_state_dict({k: state[k] for k in own})
+    model.eval().requires_grad_(False)
+    return model.to(device)
+
+
+from . import bev, chamfer, distribution, emd, eval_utils, extractor, models  # noqa: E402,F401

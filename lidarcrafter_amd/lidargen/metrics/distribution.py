@@ -1,6 +1,9 @@
 """Distances between two sets of feature vectors: the two functions of the reference's `lidargen/metrics/distribution.py`
 (`compute_frechet_distance`, `compute_squared_mmd`) with its arithmetic, on the host with numpy / scipy in the dtype of the
 inputs (the evaluator passes float64).  These are [n, 1808] matrices once per evaluation, not a hot path: no kernel.
+`calculate_frechet_distance` is the formula of the reference's `fid_score.py` (:116-167), which FSVD goes through
+(eval_utils.compute_fd): the same quantity as `compute_frechet_distance` but not the same operations (a dot product for the
+mean term, three separate traces, a regularised retry when the matrix square root is not finite), so it stands beside it.
 
 `compute_squared_mmd` takes its subsets from numpy's global generator, per subset first the rows of `feats2`, then the
 rows of `feats1` -- the reference's order, so a call after `np.random.seed(s)` gives the reference's number."""
@@ -42,3 +45,23 @@ def compute_squared_mmd(feats1, feats2, num_subsets=100, max_subset_size=1000):
         across = _poly3(x, y, width)
         total += (within.sum() - np.diag(within).sum()) / (m - 1) - across.sum() * 2 / m
     return float(total / num_subsets / m)
+
+
+def calculate_frechet_distance(mu1, sigma1, mu2, sigma2, eps=1e-6):
+    """|mu1 - mu2|^2 + tr S1 + tr S2 - 2 tr (S1 S2)^(1/2) from the moments.  A non-finite square root is retried with eps
+    added to both diagonals; an imaginary part of the root beyond 1e-3 on its diagonal raises, a smaller one is dropped."""
+    mu1, mu2 = np.atleast_1d(mu1), np.atleast_1d(mu2)
+    sigma1, sigma2 = np.atleast_2d(sigma1), np.atleast_2d(sigma2)
+    assert mu1.shape == mu2.shape, "the two mean vectors have different lengths"
+    assert sigma1.shape == sigma2.shape, "the two covariances have different dimensions"
+    diff = mu1 - mu2
+    covmean, _ = linalg.sqrtm(sigma1.dot(sigma2), disp=False)
+    if not np.isfinite(covmean).all():
+        print(f"fid calculation produces singular product; adding {eps} to diagonal of cov estimates")
+        offset = np.eye(sigma1.shape[0]) * eps
+        covmean = linalg.sqrtm((sigma1 + offset).dot(sigma2 + offset))
+    if np.iscomplexobj(covmean):
+        if not np.allclose(np.diagonal(covmean).imag, 0, atol=1e-3):
+            raise ValueError(f"Imaginary component {np.max(np.abs(covmean.imag))}")
+        covmean = covmean.real
+    return diff.dot(diff) + np.trace(sigma1) + np.trace(sigma2) - 2 * np.trace(covmean)

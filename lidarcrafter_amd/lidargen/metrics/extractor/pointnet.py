@@ -74,14 +74,17 @@ class _Folded(nn.Module):
                     fp.append((t.data_ptr(), t._version, str(t.device), t.dtype))
         return tuple(fp)
 
+    def _fold_pair(self, lin, bn):
+        """(w, b) of one layer of `_pairs()` (the sparse extractors fold a `kernel` without a bias instead)."""
+        return fold_bn(lin.weight, lin.bias, bn) if bn is not None else _plain(lin.weight, lin.bias)
+
     def folded(self):
         """[(w, b)] per layer of `_pairs()`, float32 on the parameters' device."""
         key = self._fingerprint()
         hit = self.__dict__.get("_lc_folded")
         if hit is None or hit[0] != key:
             with torch.no_grad():
-                ws = [fold_bn(l.weight, l.bias, bn) if bn is not None else _plain(l.weight, l.bias)
-                      for l, bn in self._pairs()]
+                ws = [self._fold_pair(l, bn) for l, bn in self._pairs()]
             hit = (key, ws)
             self.__dict__["_lc_folded"] = hit
             self.__dict__["_lc_work"] = {}

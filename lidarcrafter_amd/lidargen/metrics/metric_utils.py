@@ -4,9 +4,9 @@ lidargen/metrics/metric_utils.py: `ravel_hash` :28-40, `sparse_quantize` :43-66,
 (the BEV cell sets the MMD of eval_utils.compute_mmd is computed from; one bitmap per cloud, csrc/bev_chamfer.hip).
 The point sets stay on the device: sweeps are scattered with atomics (lc_bev_occupancy_accumulate),
 unique voxels come from a device radix sort (lc_sparse_quantize).  numpy in -> numpy out, CUDA
-tensors in -> CUDA tensors out.  The feature-extractor front-ends of that module (pcd2range,
-pcd2voxel, compute_logits: RangeNet++ / MinkowskiNet / SPVCNN inputs) are out of scope
-(SURVEY.md section 2 row 17)."""
+tensors in -> CUDA tensors out.  Of the feature-extractor front-ends of that module the sparse-volume one is built
+(`preprocess_pcd` :310-314, `pcd2voxel` :157-167, a collate, `compute_logits` :374-412 for 'voxel' with the depth-sector
+aggregation of `batch2list` :351-365 on the device); pcd2range and the 'range' / 'point_voxel' modalities are not."""
 from __future__ import annotations
 
 import math
@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from lidarcrafter_amd import ops as K
+from lidarcrafter_amd import ops_spconv as KS
 
 # lidargen/metrics/__init__.py:28-33
 VOXEL_SIZE = 0.05
@@ -106,3 +107,106 @@ def compute_jsd(reference, samples, data):
     r = r.cpu().numpy() if isinstance(r, torch.Tensor) else r
     s = s.cpu().numpy() if isinstance(s, torch.Tensor) else s
     return float(jensenshannon((r / np.sum(r)).flatten(), (s / np.sum(s)).flatten()))
+
+
+# ---- the sparse-volume front-end (FSVD) ---------------------------------------------------------------------------
+class SparseTensor:
+    """Rows `F` [N, C] over integer coordinates `C` [N, 3] (one cloud) or [N, 4] = (x, y, z, batch) (a collated batch)."""
+
+    def __init__(self, feats, coords, stride=1):
+        self.F, self.C, self.s = feats, coords, stride
+
+
+def preprocess_pcd(pcd, **kwargs):
+    """The rows with depth_range[0] < |p| < depth_range[1] (metric_utils.py:310-314)."""
+    lo, hi = kwargs["depth_range"]
+    if isinstance(pcd, torch.Tensor):
+        depth = torch.linalg.vector_norm(pcd, 2, dim=1)
+        return pcd[(depth > lo) & (depth < hi)]
+    depth = np.linalg.norm(pcd, 2, axis=1)
+    return pcd[np.logical_and(depth > lo, depth < hi)]
+
+
+def pcd2voxel(pcd):
+    """One cloud [N, 3] -> {'lidar': SparseTensor(F [n, 4] float32 = (x, y, z, -1) of each voxel's first point, C [n, 3]
+    = round(p / 0.05) - min, unique, in np.unique(ravel_hash) order)} (metric_utils.py:157-167).  A numpy cloud is
+    quantized on the host in numpy's own arithmetic (round half to even in the dtype of pcd / 0.05) and gives CPU tensors;
+    a CUDA tensor is quantized by lc_sparse_quantize and stays on the device."""
+    if pcd.ndim != 2 or pcd.shape[1] != 3:
+        raise ValueError(f"pcd2voxel: a cloud must be [N, 3], got {tuple(pcd.shape)}")
+    if isinstance(pcd, torch.Tensor):
+        if not pcd.is_cuda:
+            raise RuntimeError("pcd2voxel: a tensor must be a CUDA(HIP) tensor (a numpy cloud is quantized on the host)")
+        if pcd.shape[0] == 0:
+            return {"lidar": SparseTensor(pcd.new_zeros((0, 4), dtype=torch.float32),
+                                          torch.zeros((0, 3), dtype=torch.int64, device=pcd.device))}
+        v = torch.round(pcd / VOXEL_SIZE)
+        v = (v - v.min(dim=0, keepdim=True).values).float().contiguous()
+        _, inds = K.sparse_quantize(v, 1, return_index=True)
+        feat = torch.cat([pcd[inds].float(), -torch.ones((inds.numel(), 1), device=pcd.device)], dim=1)
+        return {"lidar": SparseTensor(feat, v[inds].long())}
+    if pcd.shape[0] == 0:
+        return {"lidar": SparseTensor(torch.zeros((0, 4)), torch.zeros((0, 3), dtype=torch.int64))}
+    v = np.round(pcd / VOXEL_SIZE)
+    v = v - v.min(0, keepdims=True)
+    ext = v.max(0).astype(np.uint64) + 1
+    q = v.astype(np.uint64)
+    h = (q[:, 0] * ext[1] + q[:, 1]) * ext[2] + q[:, 2]         # ravel_hash: row-major over the extents
+    _, inds = np.unique(h, return_index=True)
+    feat = np.concatenate((pcd[inds], -np.ones((inds.shape[0], 1))), axis=1)
+    return {"lidar": SparseTensor(torch.from_numpy(feat.astype(np.float32)), torch.from_numpy(v[inds].astype(np.int64)))}
+
+
+def sparse_collate(batch, device=None):
+    """[pcd2voxel(...)] -> (feats [N, 4] float32, coords [N, 4] int32 = (x, y, z, batch), offsets int32 [len + 1]) on
+    `device` (default: where the first cloud is): torchsparse's sparse_collate_fn, batch index last."""
+    ts = [b["lidar"] for b in batch]
+    if not ts:
+        raise ValueError("sparse_collate: an empty batch")
+    device = ts[0].F.device if device is None else device
+    feats = torch.cat([t.F.to(device) for t in ts]).float().contiguous()
+    coords = torch.cat([torch.cat([t.C.to(device).to(torch.int32),
+                                   torch.full((t.C.shape[0], 1), i, dtype=torch.int32, device=device)], dim=1)
+                        for i, t in enumerate(ts)]).contiguous()
+    counts = torch.tensor([0] + [t.C.shape[0] for t in ts], dtype=torch.int64)
+    return feats, coords, torch.cumsum(counts, 0).to(torch.int32).to(device)
+
+
+def sector_edges(depth_range):
+    """The 17 float32 edges of the 16 depth sectors (batch2list 'depth', metric_utils.py:357-358)."""
+    from . import NUM_SECTORS
+
+    e = torch.linspace(depth_range[0] + 3, depth_range[1], NUM_SECTORS + 1)
+    e[0] = 0.0
+    return e
+
+
+def compute_logits(data_type, modality, *args, model=None, root=None):
+    """For every list of [N, 3] clouds in `args` the float32 [n, 16 * width] matrix of depth-sector means of the
+    extractor's features (metric_utils.py:374-412), MODAL2BATCHSIZE clouds at a time.  Only 'voxel' (MinkowskiNet, FSVD)
+    is built.  `model`: a minkowskinet Model in eval mode on the GPU; None builds the pretrained one (build_model)."""
+    from . import DATASET_CONFIG, MODAL2BATCHSIZE, MODALITY2MODEL, TYPE2DATASET, build_model
+
+    assert data_type in ["32", "64"]
+    assert modality in ["range", "voxel", "point_voxel"]
+    if modality != "voxel":
+        raise NotImplementedError(f"compute_logits: modality '{modality}' ({MODALITY2MODEL[modality]}) is not built; "
+                                  "'voxel' is")
+    if not torch.cuda.is_available():
+        raise RuntimeError("compute_logits needs the MI355X: no CPU fallback on the hot path")
+    cfg = DATASET_CONFIG[TYPE2DATASET[data_type]]
+    bs = MODAL2BATCHSIZE[modality]
+    if model is None:
+        model = build_model(TYPE2DATASET[data_type], MODALITY2MODEL[modality], device="cuda", root=root)
+    dev = next(model.parameters()).device
+    edges = sector_edges(cfg["depth_range"]).to(dev)
+    output = tuple()
+    for data in args:
+        rows = []
+        for i in range(math.ceil(len(data) / bs)):
+            batch = [pcd2voxel(preprocess_pcd(pcd, **cfg)) for pcd in data[i * bs:(i + 1) * bs]]
+            feats, coords, offsets = sparse_collate(batch, dev)
+            out = model(feats, coords, return_final_logits=True)
+            rows.append(KS.sector_means(out["logits"], coords, offsets, edges, VOXEL_SIZE).cpu().numpy())
+        output += (np.concatenate(rows) if rows else np.zeros((0, 0), np.float32),)
+    return output
