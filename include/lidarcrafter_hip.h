@@ -991,6 +991,35 @@ int lc_spconv_fwd(const float* x, int64_t ldx, const int32_t* nbr, int n_in, con
 int lc_spconv_sector_means(const float* f, int64_t ldf, const int32_t* coords, const int32_t* offsets, int n_clouds,
                            int C, const float* edges, float voxel, float* out, lc_stream_t s);
 
+/* ---------------------------------------------------------------------------------------------
+ * Point <-> voxel exchanges (csrc/spvoxel.hip): what the SPVCNN of the Frechet Point-Voxel Distance
+ * (lidargen/metrics/models/spvcnn/model.py) takes from torchsparse 1.4.0 (sphashquery, calc_ti_weights, spdevoxelize,
+ * spvoxelize).  Points are rows (x, y, z, batch) of floats; a level is the lc_spconv_hash_build table of its coordinates.
+ * Limits as above (LC_EUNSUP); rows <= LC_SPCONV_MAX_ROWS.  No atomics anywhere: the same bits every run, and a point's or
+ * a voxel's bits depend on its own neighbours / points only.
+ *   lc_spvox_query: for every point the eight voxels base + {0, stride}^3, base = floor(p / stride) * stride, in the
+ *     point's own batch: idx [N, 8] int32, k = 4 ix + 2 iy + iz (kind 1 of lc_spconv_map), -1 when absent; a probe with a
+ *     component outside [0, LC_SPCONV_MAX_COORD] (or a point that is not finite) is absent before a key is formed.
+ *     w [N, 8] or NULL (idx only): a = (base + stride) - p on an axis with offset 0, p - base with offset stride;
+ *     w_k = ((a_x a_y) a_z) / stride^3, 0 where idx is -1, then w_k / (S + 1e-8) with S = ((((((w_0 + w_1) + w_2) + w_3)
+ *     + w_4) + w_5) + w_6) + w_7, every operation rounded once to float32.  A point without a neighbour gets zeros.
+ *     stride a power of two (LC_EUNSUP otherwise: the base is exact); pts, idx, w 16-byte aligned.
+ *   lc_spvox_devoxelize: out[i, :C] = (sum over k ascending with idx[i, k] in [0, n_rows) of w[i, k] f[idx[i, k], :C], an
+ *     fma chain from 0) + addend[i, :C]; f rows ldf floats apart (n_rows of them), addend rows lda apart or NULL, out rows
+ *     ldo apart.  An entry -1 or outside [0, n_rows) reads nothing and adds nothing.  addend may be out itself; out may not
+ *     overlap f.  C in {16, 48, 64, 128}; ldf, lda, ldo multiples of 4 and f, addend, out 16-byte aligned (LC_EUNSUP).
+ *   lc_spvox_voxelize: out[v, :C] = sum over j = offsets[v] .. offsets[v + 1] - 1 ascending of f[perm[j], :C] / (offsets[v
+ *     + 1] - offsets[v]), each term divided and then added to the running sum, which starts at 0: with perm the points in
+ *     voxel order (a stable sort of their voxel) the mean of a voxel's points added in ascending point order.  offsets a
+ *     device int32 [V + 1] into perm [n_perm]; a voxel without points gives zeros; an entry of perm outside [0, n_rows) adds
+ *     nothing.  C in {4, 16, 64, 128}. */
+int lc_spvox_query(const float* pts, int N, int stride, const void* table, int n_table, int32_t* idx, float* w,
+                   lc_stream_t s);
+int lc_spvox_devoxelize(const float* f, int64_t ldf, int n_rows, const int32_t* idx, const float* w, const float* addend,
+                        int64_t lda, float* out, int64_t ldo, int N, int C, lc_stream_t s);
+int lc_spvox_voxelize(const float* f, int64_t ldf, int n_rows, const int32_t* perm, int n_perm, const int32_t* offsets,
+                      int V, float* out, int64_t ldo, int C, lc_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -203,6 +203,9 @@ SIGNATURES = {
     "lc_spconv_map": (i32, [vp, i32, i32, i32, vp, i32, vp, vp]),
     "lc_spconv_fwd": (i32, [vp, i64, vp, i32, vp, vp, vp, i64, vp, i64, i32, i32, i32, i32, i32, i32, vp]),
     "lc_spconv_sector_means": (i32, [vp, i64, vp, vp, i32, i32, vp, f32, vp, vp]),
+    "lc_spvox_query": (i32, [vp, i32, i32, vp, i32, vp, vp, vp]),
+    "lc_spvox_devoxelize": (i32, [vp, i64, i32, vp, vp, vp, i64, vp, i64, i32, i32, vp]),
+    "lc_spvox_voxelize": (i32, [vp, i64, i32, vp, i32, vp, i32, vp, i64, i32, vp]),
 }
 
 _lib = None

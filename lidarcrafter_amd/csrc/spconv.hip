@@ -3,7 +3,7 @@
 // what the reference's MinkUNet (lidargen/metrics/models/minkowskinet/model.py) takes from torchsparse 1.4.0.
 //   sp_hash_insert_kernel  key = batch << 54 | x << 36 | y << 18 | z (18 bits each, 9 for the batch: non-negative as an
 //                          int64) into an open-addressing table of 64-bit keys through atomicCAS, linear probing;
-//                          value = the row.
+//                          value = the row.  (The key, the probe and the range rule: spconv_hash.h.)
 //   sp_map_kernel          nbr[j][k] = row of C[j] + offset_k in the table or -1.  A query with a component below 0 or
 //                          above LC_SPCONV_MAX_COORD is absent before any key is formed: nothing wraps into a
 //                          neighbouring field of the key, so no cloud sees another cloud's voxel.
@@ -25,6 +25,7 @@
 //                          16 depth sectors; thread (group g, channel c) sums rows g, g + G, ... into its own LDS slots,
 //                          the G partial sums are added in the order of g: no float atomics, the same bits every run.
 #include "common.h"
+#include "spconv_hash.h"
 
 namespace {
 
@@ -32,24 +33,6 @@ constexpr int SP_T = LC_SPCONV_TILE;          // output rows per block
 constexpr int SP_CK = 64;                     // input channels staged at a time
 constexpr int SP_XS = SP_CK + 4;              // row stride of the gathered tile in LDS (16-byte aligned rows)
 constexpr int SP_MAXCO = 128;
-constexpr unsigned long long SP_EMPTY = ~0ull;
-
-__device__ __forceinline__ unsigned long long sp_key(int b, int x, int y, int z) {
-    return ((unsigned long long)b << 54) | ((unsigned long long)x << 36) | ((unsigned long long)y << 18) |
-           (unsigned long long)z;
-}
-__device__ __forceinline__ bool sp_in_range(int b, int x, int y, int z) {
-    return (unsigned)b <= (unsigned)LC_SPCONV_MAX_BATCH && (unsigned)x <= (unsigned)LC_SPCONV_MAX_COORD &&
-           (unsigned)y <= (unsigned)LC_SPCONV_MAX_COORD && (unsigned)z <= (unsigned)LC_SPCONV_MAX_COORD;
-}
-__device__ __forceinline__ unsigned sp_slot(unsigned long long k, unsigned mask) {
-    k ^= k >> 33;
-    k *= 0xff51afd7ed558ccdull;
-    k ^= k >> 33;
-    k *= 0xc4ceb9fe1a85ec53ull;
-    k ^= k >> 33;
-    return (unsigned)k & mask;
-}
 
 __global__ __launch_bounds__(256) void sp_hash_clear_kernel(unsigned long long* keys, int32_t* vals, unsigned cap) {
     const unsigned i = blockIdx.x * 256u + threadIdx.x;
@@ -75,20 +58,6 @@ __global__ __launch_bounds__(256) void sp_hash_insert_kernel(const int32_t* __re
             return;
         }
     }
-}
-
-__device__ __forceinline__ int sp_find(const unsigned long long* __restrict__ keys, const int32_t* __restrict__ vals,
-                                       unsigned cap, int b, int x, int y, int z) {
-    if (!sp_in_range(b, x, y, z)) return -1;
-    const unsigned long long key = sp_key(b, x, y, z);
-    const unsigned mask = cap - 1;
-    unsigned h = sp_slot(key, mask);
-    for (unsigned probe = 0; probe < cap; ++probe, h = (h + 1) & mask) {
-        const unsigned long long k = keys[h];
-        if (k == key) return vals[h];
-        if (k == SP_EMPTY) return -1;
-    }
-    return -1;
 }
 
 // one thread per (row j, offset k)
@@ -291,12 +260,6 @@ __global__ __launch_bounds__(256) void sp_sector_kernel(const float* __restrict_
 }
 
 bool sp_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
-unsigned sp_capacity(int64_t n) {
-    unsigned cap = 1024;
-    while ((int64_t)cap < 2 * n) cap <<= 1;
-    return cap;
-}
 
 bool sp_width_in(int c) { return c == 4 || c == 16 || c == 32 || c == 48 || c == 64 || c == 96 || c == 128 || c == 192; }
 bool sp_width_out(int c) { return c == 16 || c == 32 || c == 48 || c == 64 || c == 128; }

@@ -1,7 +1,9 @@
 """Evaluation front-end on the device (SURVEY.md section 8f-3 ii): `bev`, `chamfer`, `emd`, `eval_utils.evaluate`, the
-Frechet Point Distance (`extractor.pointnet`, `distribution`, `eval_utils.compute_fpd`) and the Frechet Sparse Volume
+Frechet Point Distance (`extractor.pointnet`, `distribution`, `eval_utils.compute_fpd`), the Frechet Sparse Volume
 Distance (`models.minkowskinet`, `metric_utils.compute_logits`, `eval_utils.compute_fsvd`; sparse 3-D convolution in
-csrc/spconv.hip).  The other two learned-feature metrics of the reference (FRID: RangeNet, FPVD: SPVCNN) are not built."""
+csrc/spconv.hip) and the Frechet Point-Voxel Distance (`models.spvcnn`, `metric_utils.compute_point_voxel_logits`,
+`eval_utils.compute_fpvd`; point <-> voxel exchanges in csrc/spvoxel.hip).  The fourth learned-feature metric of the
+reference (FRID: RangeNet) is not built."""
 import os
 
 # a score line as the reference prints it: a 50-column rule above and below `|<16 blanks>NAME:1.2345E+00<17 blanks>|`
@@ -20,36 +22,46 @@ DATASET_CONFIG = {"kitti": {"size": [64, 1024], "fov": [3, -25], "depth_range": 
                   "nuscenes": {"size": [32, 1024], "fov": [10, -30], "depth_range": [1.0, 45.0]}}
 
 
-def build_model(dataset_name, model_name, device="cpu", root=None):
-    """The pretrained extractor `model_name` of `dataset_name` from <root>/<dataset_name>/<model_name>/{config.yaml,
-    model.ckpt} (root: DEFAULT_ROOT), in eval mode on `device`.  Only 'minkowskinet' is built.  Nothing is fetched: a
-    missing folder or file raises FileNotFoundError naming the path.  Unlike the reference's `strict=False` a model key
-    missing from the checkpoint raises; keys the model does not have are ignored."""
+def _load_pretrained(who, dataset_name, model_name, model_cls, device, root):
+    """`model_cls(config.yaml)` with `model.ckpt`'s state dict from <root>/<dataset_name>/<model_name>/, in eval mode on
+    `device`; `who` names the caller in the errors."""
     import torch
     import yaml
 
-    if model_name != "minkowskinet":
-        raise NotImplementedError(f"build_model: '{model_name}' is not built (only 'minkowskinet', the extractor of FSVD)")
     folder = os.path.join(DEFAULT_ROOT if root is None else os.fspath(root), dataset_name, model_name)
     if not os.path.isdir(folder):
-        raise FileNotFoundError(f"build_model: no pretrained weights folder at {folder} -- place the reference's "
+        raise FileNotFoundError(f"{who}: no pretrained weights folder at {folder} -- place the reference's "
                                 "config.yaml and model.ckpt there or pass root=<path>; this build does not fetch them")
     paths = [os.path.join(folder, n) for n in ("config.yaml", "model.ckpt")]
     for p in paths:
         if not os.path.isfile(p):
-            raise FileNotFoundError(f"build_model: {p} is missing; this build does not fetch it")
-    from .models.minkowskinet.model import Model
-
+            raise FileNotFoundError(f"{who}: {p} is missing; this build does not fetch it")
     with open(paths[0], "r") as f:
-        model = Model(yaml.safe_load(f))
+        model = model_cls(yaml.safe_load(f))
     state = torch.load(paths[1], map_location="cpu", weights_only=False)["state_dict"]
     own = model.state_dict()
     missing = [k for k in own if k not in state]
     if missing:
-        raise KeyError(f"build_model: {paths[1]} lacks {len(missing)} keys of the model, the first: {missing[:4]}")
+        raise KeyError(f"{who}: {paths[1]} lacks {len(missing)} keys of the model, the first: {missing[:4]}")
     model.load_state_dict({k: state[k] for k in own})
     model.eval().requires_grad_(False)
     return model.to(device)
+
+
+def build_model(dataset_name, model_name, device="cpu", root=None):
+    """The pretrained extractor `model_name` of `dataset_name` from <root>/<dataset_name>/<model_name>/{config.yaml,
+    model.ckpt} (root: DEFAULT_ROOT), in eval mode on `device`.  Only 'minkowskinet' is built here ('spvcnn' has its own
+    loader, models.spvcnn.pretrained).  Nothing is fetched: a missing folder or file raises FileNotFoundError naming the
+    path.  Unlike the reference's `strict=False` a model key missing from the checkpoint raises; keys the model does not
+    have are ignored."""
+    if model_name == "spvcnn":
+        raise NotImplementedError("build_model: 'spvcnn' is not dispatched from here; the extractor of FPVD is loaded by "
+                                  "models.spvcnn.pretrained(dataset_name, device, root)")
+    if model_name != "minkowskinet":
+        raise NotImplementedError(f"build_model: '{model_name}' is not built (only 'minkowskinet', the extractor of FSVD)")
+    from .models.minkowskinet.model import Model
+
+    return _load_pretrained("build_model", dataset_name, model_name, Model, device, root)
 
 
 from . import bev, chamfer, distribution, emd, eval_utils, extractor, models  # noqa: E402,F401

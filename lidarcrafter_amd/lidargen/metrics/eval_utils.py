@@ -1,9 +1,10 @@
 """Evaluation front-end -- mirror of the reference's `lidargen/metrics/eval_utils.py`: `evaluate(reference, samples,
 metrics, data)` and the weight-free scores behind it (`compute_cd` :40-51, `compute_emd` :54-65, `compute_mmd` :68-82,
 `compute_jsd` :85-95).  Every score is printed through the reference's OUTPUT_TEMPLATE and also returned; `evaluate`
-returns {metric: score}.  Of the perceptual metrics FSVD is built (`compute_fd` :98-102, `compute_fsvd` :116-124: MinkUNet
-features, sparse convolution in csrc/spconv.hip); FRID and FPVD are not.  `evaluate` still refuses all three and 'mmd'
-(its callers rely on that): call `compute_fsvd` / `compute_mmd` directly.
+returns {metric: score}.  Of the perceptual metrics FSVD and FPVD are built (`compute_fd` :98-102, `compute_fsvd` :116-124:
+MinkUNet features, sparse convolution in csrc/spconv.hip; `compute_fpvd` :127-135: SPVCNN features, point <-> voxel
+exchanges in csrc/spvoxel.hip); FRID is not.  `evaluate` still refuses all three and 'mmd' (its callers rely on that):
+call `compute_fsvd` / `compute_fpvd` / `compute_mmd` directly.
 
 `extract_point_features` / `compute_fpd` are the Frechet Point Distance of the reference's own evaluator
 (tools/evaluation/evaluate_our.py `EvaluationEngine`: PointNet1 features of every cloud, `distribution.
@@ -18,7 +19,8 @@ from . import distribution, metric_utils
 from .chamfer import bev_min_matching, compute_pairwise_cd
 from .emd import compute_pairwise_emd_batch
 
-_NOT_BUILT = {"frid": "the pretrained range-image extractor", "fpvd": "the pretrained point-voxel extractor",
+_NOT_BUILT = {"frid": "the pretrained range-image extractor",
+              "fpvd": "a direct call of eval_utils.compute_fpvd(reference, samples, data)",
               "fsvd": "a direct call of eval_utils.compute_fsvd(reference, samples, data)",
               "mmd": "a direct call of eval_utils.compute_mmd(reference, samples, data)"}
 
@@ -27,8 +29,8 @@ def evaluate(reference, samples, metrics, data):
     scores = {}
     for m in ("frid", "fsvd", "fpvd"):   # perceptual
         if m in metrics:
-            if m == "fsvd":
-                raise NotImplementedError(f"evaluate: metric 'fsvd' is not dispatched from here; it needs {_NOT_BUILT[m]}")
+            if m in ("fsvd", "fpvd"):
+                raise NotImplementedError(f"evaluate: metric '{m}' is not dispatched from here; it needs {_NOT_BUILT[m]}")
             raise NotImplementedError(f"evaluate: metric '{m}' needs {_NOT_BUILT[m]}, which this build does not have")
     if "mmd" in metrics:
         raise NotImplementedError(f"evaluate: metric 'mmd' is not dispatched from here; it needs {_NOT_BUILT['mmd']}")
@@ -150,4 +152,14 @@ def compute_fsvd(reference, samples, data, model=None):
     gt_logits, samples_logits = metric_utils.compute_logits(data, "voxel", reference, samples, model=model)
     score = compute_fd(gt_logits, samples_logits)
     print(OUTPUT_TEMPLATE.format("FSVD", score))
+    return score
+
+
+def compute_fpvd(reference, samples, data, model=None):
+    """Score of Frechet Point-Voxel Distance (FPVD): the Frechet distance of the depth-sector means of the SPVCNN
+    features of the two sets of [N, 3] clouds.  `model`: the extractor to use instead of the pretrained one."""
+    print("Evaluating (FPVD) ...")
+    gt_logits, samples_logits = metric_utils.compute_point_voxel_logits(data, reference, samples, model=model)
+    score = compute_fd(gt_logits, samples_logits)
+    print(OUTPUT_TEMPLATE.format("FPVD", score))
     return score

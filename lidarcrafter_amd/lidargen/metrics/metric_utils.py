@@ -6,7 +6,9 @@ The point sets stay on the device: sweeps are scattered with atomics (lc_bev_occ
 unique voxels come from a device radix sort (lc_sparse_quantize).  numpy in -> numpy out, CUDA
 tensors in -> CUDA tensors out.  Of the feature-extractor front-ends of that module the sparse-volume one is built
 (`preprocess_pcd` :310-314, `pcd2voxel` :157-167, a collate, `compute_logits` :374-412 for 'voxel' with the depth-sector
-aggregation of `batch2list` :351-365 on the device); pcd2range and the 'range' / 'point_voxel' modalities are not."""
+aggregation of `batch2list` :351-365 on the device) and the point-voxel one (`compute_point_voxel_logits`: the same
+input and aggregation around the SPVCNN); pcd2range and the 'range' modality are not.  `compute_logits` still refuses
+'point_voxel' by name (its callers rely on that) and points at `compute_point_voxel_logits`."""
 from __future__ import annotations
 
 import math
@@ -181,27 +183,17 @@ def sector_edges(depth_range):
     return e
 
 
-def compute_logits(data_type, modality, *args, model=None, root=None):
-    """For every list of [N, 3] clouds in `args` the float32 [n, 16 * width] matrix of depth-sector means of the
-    extractor's features (metric_utils.py:374-412), MODAL2BATCHSIZE clouds at a time.  Only 'voxel' (MinkowskiNet, FSVD)
-    is built.  `model`: a minkowskinet Model in eval mode on the GPU; None builds the pretrained one (build_model)."""
-    from . import DATASET_CONFIG, MODAL2BATCHSIZE, MODALITY2MODEL, TYPE2DATASET, build_model
+def _sector_features(data_type, modality, model, sets):
+    """Per list of [N, 3] clouds in `sets` the float32 [n, 16 * width] depth-sector means of `model`'s features,
+    MODAL2BATCHSIZE[modality] clouds at a time."""
+    from . import DATASET_CONFIG, MODAL2BATCHSIZE, TYPE2DATASET
 
-    assert data_type in ["32", "64"]
-    assert modality in ["range", "voxel", "point_voxel"]
-    if modality != "voxel":
-        raise NotImplementedError(f"compute_logits: modality '{modality}' ({MODALITY2MODEL[modality]}) is not built; "
-                                  "'voxel' is")
-    if not torch.cuda.is_available():
-        raise RuntimeError("compute_logits needs the MI355X: no CPU fallback on the hot path")
     cfg = DATASET_CONFIG[TYPE2DATASET[data_type]]
     bs = MODAL2BATCHSIZE[modality]
-    if model is None:
-        model = build_model(TYPE2DATASET[data_type], MODALITY2MODEL[modality], device="cuda", root=root)
     dev = next(model.parameters()).device
     edges = sector_edges(cfg["depth_range"]).to(dev)
     output = tuple()
-    for data in args:
+    for data in sets:
         rows = []
         for i in range(math.ceil(len(data) / bs)):
             batch = [pcd2voxel(preprocess_pcd(pcd, **cfg)) for pcd in data[i * bs:(i + 1) * bs]]
@@ -210,3 +202,42 @@ def compute_logits(data_type, modality, *args, model=None, root=None):
             rows.append(KS.sector_means(out["logits"], coords, offsets, edges, VOXEL_SIZE).cpu().numpy())
         output += (np.concatenate(rows) if rows else np.zeros((0, 0), np.float32),)
     return output
+
+
+def compute_logits(data_type, modality, *args, model=None, root=None):
+    """For every list of [N, 3] clouds in `args` the float32 [n, 16 * width] matrix of depth-sector means of the
+    extractor's features (metric_utils.py:374-412), MODAL2BATCHSIZE clouds at a time.  Only 'voxel' (MinkowskiNet, FSVD)
+    is dispatched from here; 'point_voxel' (SPVCNN, FPVD) is `compute_point_voxel_logits`.  `model`: a minkowskinet Model
+    in eval mode on the GPU; None builds the pretrained one (build_model)."""
+    from . import MODALITY2MODEL, TYPE2DATASET, build_model
+
+    assert data_type in ["32", "64"]
+    assert modality in ["range", "voxel", "point_voxel"]
+    if modality == "point_voxel":
+        raise NotImplementedError(f"compute_logits: modality '{modality}' ({MODALITY2MODEL[modality]}) is not dispatched "
+                                  "from here; call metric_utils.compute_point_voxel_logits(data_type, *sets)")
+    if modality != "voxel":
+        raise NotImplementedError(f"compute_logits: modality '{modality}' ({MODALITY2MODEL[modality]}) is not built; "
+                                  "'voxel' is, and 'point_voxel' through compute_point_voxel_logits")
+    if not torch.cuda.is_available():
+        raise RuntimeError("compute_logits needs the MI355X: no CPU fallback on the hot path")
+    if model is None:
+        model = build_model(TYPE2DATASET[data_type], MODALITY2MODEL[modality], device="cuda", root=root)
+    return _sector_features(data_type, modality, model, args)
+
+
+def compute_point_voxel_logits(data_type, *sets, model=None, root=None):
+    """For every list of [N, 3] clouds in `sets` the float32 [n, 16 * 48 = 768] matrix of depth-sector means of the
+    SPVCNN's per-point features (the reference's compute_logits for 'point_voxel'), 25 clouds at a time.  The points are
+    the unique voxels of pcd2voxel; their sector is decided from the integer voxel coordinate (the
+    reference feeds the float coordinate, which is that integer or 1 ulp above it).  `model`: a spvcnn Model in eval mode
+    on the GPU; None loads the pretrained one (models.spvcnn.pretrained)."""
+    from . import TYPE2DATASET
+    from .models import spvcnn
+
+    assert data_type in ["32", "64"]
+    if not torch.cuda.is_available():
+        raise RuntimeError("compute_point_voxel_logits needs the MI355X: no CPU fallback on the hot path")
+    if model is None:
+        model = spvcnn.pretrained(TYPE2DATASET[data_type], device="cuda", root=root)
+    return _sector_features(data_type, "point_voxel", model, sets)

@@ -1,2 +1,3 @@
 """Pretrained feature extractors of the perceptual scores (the reference's `lidargen/metrics/models`): MinkowskiNet for
-FSVD.  RangeNet (FRID) and SPVCNN (FPVD) are not built."""
+FSVD, SPVCNN for FPVD.  RangeNet (FRID) is not built."""
+from . import spvcnn  # noqa: E402,F401  (models.spvcnn.pretrained)

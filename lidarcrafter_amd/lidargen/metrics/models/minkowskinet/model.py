@@ -95,22 +95,68 @@ class Model(_Folded):
         return fold_conv_bn(conv, bn)
 
     # ---- forward --------------------------------------------------------------------------------------------------
-    def forward(self, feats: torch.Tensor, coords: torch.Tensor, return_logits=False, return_final_logits=True):
-        """feats [N, input_dims] float32 and coords [N, 4] = (x, y, z, batch) of the collated batch, on the GPU ->
-        {'logits' [N, cs[8]], 'coords' [N, 3], 'batch_indices' [N]} over the input voxels in input order (the reference's
-        `return_final_logits=True`); `return_logits=True`: the bottleneck features and their batch indices."""
+    def _check_inputs(self, feats, coords, return_logits, return_final_logits):
         if self.training:
             raise RuntimeError("Model: inference only -- call .eval() first (BatchNorm batch statistics are not built)")
         for t, n in ((feats, "feats"), (coords, "coords")):
             if not isinstance(t, torch.Tensor) or not t.is_cuda:
                 raise RuntimeError(f"Model: `{n}` must be a CUDA(HIP) tensor -- no CPU fallback on the hot path")
         if not (return_logits or return_final_logits):
-            raise NotImplementedError("Model: the classifier head is not on the path of the Frechet Sparse Volume "
-                                      "Distance and is not built; pass return_final_logits=True")
+            raise NotImplementedError("Model: the classifier head is not on the path of the Frechet distances "
+                                      "and is not built; pass return_final_logits=True")
         if feats.dim() != 2 or coords.dim() != 2 or coords.shape[1] != 4 or coords.shape[0] != feats.shape[0] or \
                 feats.shape[0] < 1:
             raise ValueError(f"Model: feats [N, C] and coords [N, 4] expected, got {tuple(feats.shape)}, "
                              f"{tuple(coords.shape)}")
+
+    def _layer_ops(self):
+        """(conv, block): one folded layer / one residual block through the sparse convolution kernel."""
+        W = {id(conv): wb for (conv, _), wb in zip(self._pairs(), self.folded())}
+
+        def conv(m, x, nbr, relu, res=None, out=None, col=0):
+            w, b = W[id(m)]
+            y = KS.sparse_conv(x, nbr, w, b, residual=res, relu=relu, out=out, out_col=col)
+            return y[:, col:col + w.shape[2]]
+
+        def block(blk, x, nbr, out=None, col=0):
+            h = conv(blk.net[0], x, nbr, True)
+            r = x if len(blk.downsample) == 0 else conv(blk.downsample[0], x, None, False)
+            return conv(blk.net[3], h, nbr, True, res=r, out=out, col=col)
+
+        return conv, block
+
+    def _cat_buffers(self, L, dev):
+        """cat[i]: the input of up{i}[1] at level 4 - i = [the up-sampled rows | the skip of that level]"""
+        cs = self.cs
+        return {i: torch.empty((L.rows(4 - i), cs[4 + i] + cs[4 - i]), device=dev, dtype=torch.float32)
+                for i in range(1, 5)}
+
+    def _up(self, i, x, L, cat, conv, block):
+        """up{i}: the transposed convolution into the left columns of cat[i], then the two residual blocks."""
+        up = getattr(self, f"up{i}")
+        lvl = 4 - i
+        conv(up[0].net[0], x, L.up(lvl), True, out=cat[i], col=0)
+        x = block(up[1][0], cat[i], L.same(lvl))
+        return block(up[1][1], x, L.same(lvl))
+
+    def _stages(self, x, L, cat, conv, block):
+        """stage1 .. stage4 from the level-0 rows x; the skips of levels 1 .. 3 land in their cat buffers."""
+        cs = self.cs
+        for i in range(1, 5):
+            stage = getattr(self, f"stage{i}")
+            x = conv(stage[0].net[0], x, L.down(i - 1), True)
+            x = block(stage[1], x, L.same(i))
+            if i < 4:
+                x = block(stage[2], x, L.same(i), out=cat[4 - i], col=cs[8 - i])
+            else:
+                x = block(stage[2], x, L.same(i))
+        return x
+
+    def forward(self, feats: torch.Tensor, coords: torch.Tensor, return_logits=False, return_final_logits=True):
+        """feats [N, input_dims] float32 and coords [N, 4] = (x, y, z, batch) of the collated batch, on the GPU ->
+        {'logits' [N, cs[8]], 'coords' [N, 3], 'batch_indices' [N]} over the input voxels in input order (the reference's
+        `return_final_logits=True`); `return_logits=True`: the bottleneck features and their batch indices."""
+        self._check_inputs(feats, coords, return_logits, return_final_logits)
         cs, dev = self.cs, feats.device
         with torch.cuda.device(dev), torch.no_grad():
             feats = feats.float().contiguous()
@@ -118,39 +164,15 @@ class Model(_Folded):
             top = coords.max(dim=0).values.tolist()          # one read: the limits are checked on the host
             if int(coords.min().item()) < 0:
                 raise ValueError("Model: negative coordinates (pcd2voxel subtracts the minimum)")
-            W = {id(conv): wb for (conv, _), wb in zip(self._pairs(), self.folded())}
+            conv, block = self._layer_ops()
             L = KS.CoordLevels(coords, n_batch=top[3] + 1, max_coord=max(top[:3]))
-
-            def conv(m, x, nbr, relu, res=None, out=None, col=0):
-                w, b = W[id(m)]
-                y = KS.sparse_conv(x, nbr, w, b, residual=res, relu=relu, out=out, out_col=col)
-                return y[:, col:col + w.shape[2]]
-
-            def block(blk, x, nbr, out=None, col=0):
-                h = conv(blk.net[0], x, nbr, True)
-                r = x if len(blk.downsample) == 0 else conv(blk.downsample[0], x, None, False)
-                return conv(blk.net[3], h, nbr, True, res=r, out=out, col=col)
-
-            # cat[i]: the input of up{i}[1] at level 4 - i = [the up-sampled rows | the skip of that level]
-            cat = {i: torch.empty((L.rows(4 - i), cs[4 + i] + cs[4 - i]), device=dev, dtype=torch.float32)
-                   for i in range(1, 5)}
+            cat = self._cat_buffers(L, dev)
             same0 = L.same(0)
             x = conv(self.stem[0], feats, same0, True)
             x = conv(self.stem[3], x, same0, True, out=cat[4], col=cs[8])
-            for i in range(1, 5):
-                stage = getattr(self, f"stage{i}")
-                x = conv(stage[0].net[0], x, L.down(i - 1), True)
-                x = block(stage[1], x, L.same(i))
-                if i < 4:
-                    x = block(stage[2], x, L.same(i), out=cat[4 - i], col=cs[8 - i])
-                else:
-                    x = block(stage[2], x, L.same(i))
+            x = self._stages(x, L, cat, conv, block)
             if return_logits:
                 return {"logits": x, "batch_indices": L.coords[4][:, 3]}
             for i in range(1, 5):
-                up = getattr(self, f"up{i}")
-                lvl = 4 - i
-                conv(up[0].net[0], x, L.up(lvl), True, out=cat[i], col=0)
-                x = block(up[1][0], cat[i], L.same(lvl))
-                x = block(up[1][1], x, L.same(lvl))
+                x = self._up(i, x, L, cat, conv, block)
         return {"logits": x, "coords": coords[:, :3], "batch_indices": coords[:, 3]}

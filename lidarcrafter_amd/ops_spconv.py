@@ -81,10 +81,10 @@ def kernel_map(coords: torch.Tensor, kind: int, stride: int, table: torch.Tensor
     return nbr
 
 
-def _rows(t: torch.Tensor, name: str):
+def _rows(t: torch.Tensor, name: str, who: str = "sparse_conv"):
     _req(t, name)
     if t.dim() != 2 or t.stride(1) != 1 or t.shape[0] < 1:
-        raise ValueError(f"sparse_conv: `{name}` must be [N, C] rows with unit column stride, got {tuple(t.shape)} "
+        raise ValueError(f"{who}: `{name}` must be [N, C] rows with unit column stride, got {tuple(t.shape)} "
                          f"strides {t.stride()}")
     return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
 
