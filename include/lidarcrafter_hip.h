@@ -32,7 +32,8 @@ extern "C" {
 
 typedef void* lc_stream_t;
 
-/* Library / device probe.  Returns the ABI version (this header = 5: the up-path fold's entry points, lc_up2_combine9_fwd / lc_split_act_fwd; 4: the
+/* Library / device probe.  Returns the ABI version (this header = 6: lc_sparse_quantize takes its voxel sizes as doubles;
+ * 5: the up-path fold's entry points, lc_up2_combine9_fwd / lc_split_act_fwd; 4: the
  * unit-form attention; 3: round 6 -- lc_conv2d_ring_f16x2_ps_fwd carries
  * gn_ostats_unit, the stride-2 / calibration entry points exist; 2: round 3 -- field-of-view arguments are doubles,
  * lc_layout_condition takes float32 or float64 boxes, float64 point sets).  Bumped whenever an exported signature
@@ -683,7 +684,8 @@ int lc_groupnorm_bwd_train(const float* x, int64_t x_bs, const float* dy, int64_
  *   `stamps` [nx*ny] int32 (zero-initialised by the caller, one per grid) holds the id of the last
  *   sweep that touched the voxel; pass a `stamp` != 0 that differs from sweep to sweep, and run
  *   the sweeps of one grid in stream order.  pt_stride = floats per point row (>= 2).
- * lc_sparse_quantize (:28-66): floor(coords / voxel) -> int32 [N, D] (D = 2 or 3), unique rows in
+ * lc_sparse_quantize (:28-66): floor(coords / voxel) -> int32 [N, D] (D = 2 or 3; the float64 quotient of
+ *   the float32 coordinate by the DOUBLE voxel size, as numpy divides by a float64 array), unique rows in
  *   ravel-hash (= lexicographic) order -> out_coords (first *out_count rows valid), out_index =
  *   index of each unique row's FIRST occurrence (may be NULL), out_inverse [N] (may be NULL) --
  *   np.unique(ravel_hash(q), return_index, return_inverse).  out_count: device uint64.
@@ -693,7 +695,7 @@ int lc_bev_occupancy_accumulate(const float* pts, int pt_stride, int N, float x0
                                 float y1, float voxel, int min_bound_x, int min_bound_y, int nx,
                                 int ny, int stamp, int32_t* stamps, float* grid, lc_stream_t s);
 int64_t lc_sparse_quantize_scratch_bytes(int N, int D);
-int lc_sparse_quantize(const float* coords, int N, int D, float vx, float vy, float vz, void* scratch,
+int lc_sparse_quantize(const float* coords, int N, int D, double vx, double vy, double vz, void* scratch,
                        int32_t* out_coords, int64_t* out_index, int64_t* out_inverse,
                        uint64_t* out_count, lc_stream_t s);
 
@@ -959,7 +961,8 @@ int lc_pointnet_trunk_fwd(const float* x, int64_t x_bs, const float* trans, cons
  * the caller states `max_coord` (the largest spatial entry) and `n_batch`; a row outside the limits all the same is never
  * inserted and never found.  A query at C + offset outside [0, LC_SPCONV_MAX_COORD] is absent: it never aliases another
  * batch's voxel and never wraps.
- *   lc_spconv_hash_build: table (lc_spconv_hash_bytes(N) bytes, 8-byte aligned) <- the rows of coords.
+ *   lc_spconv_hash_build: table (lc_spconv_hash_bytes(N) bytes, 8-byte aligned) <- the rows of coords.  The table's bytes
+ *     are a function of the rows alone (of equal rows the last one is found): the same for every run.
  *   lc_spconv_map: nbr [M, K] int32 <- for every row of coords [M, 4] the table row at coords + offset_k, -1 when absent;
  *     `table` built from n_table rows.  kind 0: K = 27, offsets {-stride, 0, stride}^3, k = ix + 3 iy + 9 iz.
  *     kind 1: K = 8, offsets {0, stride}^3, k = 4 ix + 2 iy + iz (coords coarse at 2 stride, table fine at stride).

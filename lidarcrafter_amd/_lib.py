@@ -173,7 +173,7 @@ SIGNATURES = {
     "lc_bev_occupancy_accumulate": (i32, [vp, i32, i32, f32, f32, f32, f32, f32, i32, i32, i32, i32,
                                           i32, vp, vp, vp]),
     "lc_sparse_quantize_scratch_bytes": (i64, [i32, i32]),
-    "lc_sparse_quantize": (i32, [vp, i32, i32, f32, f32, f32, vp, vp, vp, vp, vp, vp]),
+    "lc_sparse_quantize": (i32, [vp, i32, i32, f64, f64, f64, vp, vp, vp, vp, vp, vp]),
     "lc_bev_histogram": (i32, [vp, i32, i32, vp, i32, f32, f32, vp, vp, vp]),
     "lc_rbf_partials_elems": (i64, [i32, i32]),
     "lc_rbf_kernel_sum": (i32, [vp, vp, i32, i32, i32, f32, vp, vp]),
@@ -209,7 +209,7 @@ SIGNATURES = {
 }
 
 _lib = None
-ABI_VERSION = 5   # include/lidarcrafter_hip.h lc_abi_version: bumped with every change of an exported signature
+ABI_VERSION = 6   # include/lidarcrafter_hip.h lc_abi_version: bumped with every change of an exported signature
 
 
 class HipLibraryMissing(RuntimeError):

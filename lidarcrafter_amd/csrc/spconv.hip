@@ -2,8 +2,10 @@
 // kinds of neighbour table, one output-stationary convolution kernel and the depth-sector means of the features --
 // what the reference's MinkUNet (lidargen/metrics/models/minkowskinet/model.py) takes from torchsparse 1.4.0.
 //   sp_hash_insert_kernel  key = batch << 54 | x << 36 | y << 18 | z (18 bits each, 9 for the batch: non-negative as an
-//                          int64) into an open-addressing table of 64-bit keys through atomicCAS, linear probing;
-//                          value = the row.  (The key, the probe and the range rule: spconv_hash.h.)
+//                          int64) into an open-addressing table of 64-bit keys through atomicMin, linear probing, the
+//                          smaller key keeps a contested slot: one arrangement whatever the order of the threads.
+//   sp_hash_value_kernel   value = the row (the largest of equal ones), once the keys stand.  (The key, the probe and
+//                          the range rule: spconv_hash.h.)
 //   sp_map_kernel          nbr[j][k] = row of C[j] + offset_k in the table or -1.  A query with a component below 0 or
 //                          above LC_SPCONV_MAX_COORD is absent before any key is formed: nothing wraps into a
 //                          neighbouring field of the key, so no cloud sees another cloud's voxel.
@@ -42,21 +44,46 @@ __global__ __launch_bounds__(256) void sp_hash_clear_kernel(unsigned long long* 
     }
 }
 
+// Ordered insertion (Amble & Knuth 1974): of two keys that meet in a slot the smaller one stays and the thread carries the
+// larger one on (the empty marker is the largest value, so one atomicMin does both).  Every stored key then has only
+// smaller keys between its home slot and its own, and a set of keys has exactly one such arrangement: the table's bytes
+// do not depend on the order in which the threads arrive.  (With a plain compare-and-swap two keys of one home slot took
+// the slots in the order of arrival: the same maps, other bytes from run to run.)  sp_find needs no change: a key is
+// still reachable from its home slot over occupied slots.
 __global__ __launch_bounds__(256) void sp_hash_insert_kernel(const int32_t* __restrict__ coords, int N,
-                                                            unsigned long long* keys, int32_t* vals, unsigned cap) {
+                                                            unsigned long long* keys, unsigned cap) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= N) return;
     const int x = coords[4 * i], y = coords[4 * i + 1], z = coords[4 * i + 2], b = coords[4 * i + 3];
     if (!sp_in_range(b, x, y, z)) return;     // (the host entry refuses such inputs; a row outside is never found)
+    unsigned long long key = sp_key(b, x, y, z);
+    const unsigned mask = cap - 1;
+    unsigned h = sp_slot(key, mask);
+    for (unsigned probe = 0; probe < cap; ++probe, h = (h + 1) & mask) {
+        const unsigned long long prev = atomicMin(&keys[h], key);
+        if (prev == SP_EMPTY || prev == key) return;
+        if (prev > key) key = prev;           // the slot keeps the smaller key, the displaced one moves on
+    }
+}
+
+// the rows of the finished keys, in a launch of its own (a key may move while keys are still being inserted)
+__global__ __launch_bounds__(256) void sp_hash_value_kernel(const int32_t* __restrict__ coords, int N,
+                                                           const unsigned long long* __restrict__ keys, int32_t* vals,
+                                                           unsigned cap) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= N) return;
+    const int x = coords[4 * i], y = coords[4 * i + 1], z = coords[4 * i + 2], b = coords[4 * i + 3];
+    if (!sp_in_range(b, x, y, z)) return;
     const unsigned long long key = sp_key(b, x, y, z);
     const unsigned mask = cap - 1;
     unsigned h = sp_slot(key, mask);
     for (unsigned probe = 0; probe < cap; ++probe, h = (h + 1) & mask) {
-        const unsigned long long prev = atomicCAS(&keys[h], SP_EMPTY, key);
-        if (prev == SP_EMPTY || prev == key) {
+        const unsigned long long k = keys[h];
+        if (k == key) {
             atomicMax(&vals[h], i);           // (rows are unique by contract; of equal ones the last wins, every run)
             return;
         }
+        if (k == SP_EMPTY) return;
     }
 }
 
@@ -280,7 +307,8 @@ extern "C" int lc_spconv_hash_build(const int32_t* coords, int N, int max_coord,
     unsigned long long* keys = static_cast<unsigned long long*>(table);
     int32_t* vals = reinterpret_cast<int32_t*>(keys + cap);
     hipLaunchKernelGGL(sp_hash_clear_kernel, dim3((cap + 255) / 256), dim3(256), 0, lc_s(s), keys, vals, cap);
-    hipLaunchKernelGGL(sp_hash_insert_kernel, dim3((N + 255) / 256), dim3(256), 0, lc_s(s), coords, N, keys, vals, cap);
+    hipLaunchKernelGGL(sp_hash_insert_kernel, dim3((N + 255) / 256), dim3(256), 0, lc_s(s), coords, N, keys, cap);
+    hipLaunchKernelGGL(sp_hash_value_kernel, dim3((N + 255) / 256), dim3(256), 0, lc_s(s), coords, N, keys, vals, cap);
     return lc_launch_status();
 }
 

@@ -1,8 +1,9 @@
 // The coordinate hash of the sparse kernels (spconv.hip builds it and reads it for the neighbour tables, spvoxel.hip reads
 // it for the point <-> voxel maps): key = batch << 54 | x << 36 | y << 18 | z (18 bits each, 9 for the batch: non-negative
-// as an int64) in an open-addressing table of 64-bit keys, linear probing; value = the row.  A query with a component
-// below 0 or above LC_SPCONV_MAX_COORD is absent before any key is formed: nothing wraps into a neighbouring field of the
-// key, so no cloud sees another cloud's voxel.
+// as an int64) in an open-addressing table of 64-bit keys, linear probing (ordered: between a key's home slot and its
+// own there are only smaller keys, which fixes the arrangement; a search does not use the order); value = the row.  A
+// query with a component below 0 or above LC_SPCONV_MAX_COORD is absent before any key is formed: nothing wraps into a
+// neighbouring field of the key, so no cloud sees another cloud's voxel.
 #pragma once
 #include "common.h"
 

@@ -31,6 +31,8 @@ __global__ __launch_bounds__(256) void bev_occupancy_kernel(const float* __restr
     if (i >= N) return;
     const float x = pts[(long long)i * stride], y = pts[(long long)i * stride + 1];
     if (!(x > x0 && x < x1 && y > y0 && y < y1)) return;              // metric_utils.py:243-246
+    // float32 is right here: the reference divides a float32 array by a Python scalar, which numpy
+    // keeps in float32 (sparse_quantize below divides by a float64 ARRAY and takes a double voxel)
     const int ix = (int)floorf(x / voxel) - minbx, iy = (int)floorf(y / voxel) - minby;
     if (ix < 0 || ix >= nx || iy < 0 || iy >= ny) return;              // (numpy would raise)
     const int v = ix * ny + iy;
@@ -39,16 +41,18 @@ __global__ __launch_bounds__(256) void bev_occupancy_kernel(const float* __restr
 
 // ---- sparse_quantize ---------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void sq_floor_minmax_kernel(const float* __restrict__ c, int N, int D,
-                                                             float vx, float vy, float vz,
+                                                             double vx, double vy, double vz,
                                                              int* __restrict__ q, int* __restrict__ mm) {
     // q = floor(coords / voxel) as int32; mm[0..2] = per-dim min, mm[3..5] = per-dim max
     const int i = blockIdx.x * 256 + threadIdx.x;
     int lo[3] = {INT_MAX, INT_MAX, INT_MAX}, hi[3] = {INT_MIN, INT_MIN, INT_MIN};
     if (i < N) {
-        const float vs[3] = {vx, vy, vz};
+        const double vs[3] = {vx, vy, vz};
         for (int d = 0; d < D; ++d) {
-            // numpy: float32 coords / float64 voxel array -> float64 quotient, floor, astype(int32)
-            const int v = (int)floor((double)c[(long long)i * D + d] / (double)vs[d]);
+            // numpy: float32 coords / float64 voxel array -> float64 quotient, floor, astype(int32).
+            // The voxel is the caller's double, never rounded to float32: 0.5 / 0.1 floors to 5,
+            // 0.5 / (double)0.1f to 4
+            const int v = (int)floor((double)c[(long long)i * D + d] / vs[d]);
             q[(long long)i * D + d] = v;
             lo[d] = hi[d] = v;
         }
@@ -166,11 +170,11 @@ extern "C" int64_t lc_sparse_quantize_scratch_bytes(int N, int D) {
                      4 * align256((size_t)N * 4) + align256(sq_tmp_bytes(N)));
 }
 
-extern "C" int lc_sparse_quantize(const float* coords, int N, int D, float vx, float vy, float vz,
+extern "C" int lc_sparse_quantize(const float* coords, int N, int D, double vx, double vy, double vz,
                                   void* scratch, int32_t* out_coords, int64_t* out_index,
                                   int64_t* out_inverse, uint64_t* out_count, lc_stream_t s) {
     if (!coords || !scratch || !out_coords || !out_count || N <= 0 || (D != 2 && D != 3) ||
-        !(vx > 0.f) || !(vy > 0.f) || (D == 3 && !(vz > 0.f)))
+        !(vx > 0.0) || !(vy > 0.0) || (D == 3 && !(vz > 0.0)))
         return LC_EINVAL;
     hipStream_t st = lc_s(s);
     SqScratch w = sq_carve(scratch, N, D);

@@ -166,4 +166,4 @@ def test_symbols_in_header_binding_and_library():
         assert name in _lib.SIGNATURES
         assert hasattr(h, name)
     assert "emd.hip" in build.SOURCES
-    assert h.lc_abi_version() == 5 and _lib.ABI_VERSION == 5
+    assert h.lc_abi_version() == 6 and _lib.ABI_VERSION == 6

@@ -2,6 +2,11 @@
 Volume Distance front-end, against the float64 restatement of tests/_spconv_oracle.py (itself pinned on conv3d /
 conv_transpose3d by tests/test_spconv_host.py).  `pytest -m gpu`.
 
+The coordinate hash is tested on its own: the table is read back and checked against the hash restated in numpy
+(tests/_spconv_hash.py `table_invariants`) and the three neighbour tables against the oracle's dictionary, exactly, on scenes
+at the capacity boundaries, with a probe chain that wraps the end of the table, with repeated rows, at the top of every
+field of the key and at one sweep's size.
+
 Tolerances: the oracle runs the same arithmetic in float32; the row-wise rel-L2 of that against float64 is measured at run
 time and the kernel may be 4 x as far off (another summation order over up to 27 x 192 terms), never less than TOL_CONV."""
 import functools
@@ -13,6 +18,7 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import _spconv_hash as H  # noqa: E402
 import _spconv_oracle as O  # noqa: E402
 
 from lidarcrafter_amd import ops_spconv as KS  # noqa: E402
@@ -86,6 +92,111 @@ def test_maps_equal_the_oracles(dev, s):
     assert lv.same(0) is lv.same(0)                                  # built once
 
 
+# ---- the coordinate hash: load, probing, duplicates, the top of every field ---------------------------------------------
+def _check_hash_scene(dev, c, s, n_batch, oracle=O, extra=None):
+    """The table of c [N, 4] int64 read back (`H.table_invariants`), and the three kinds of neighbour table exactly as the
+    oracle has them -- a dictionary over the rows, never the hash.  `extra`: further query rows (not in the table) for
+    the kinds that take any query.  -> what table_invariants returns, and the `same` table."""
+    cd = c.to(torch.int32).to(dev)
+    n = len(c)
+    table = KS.hash_build(cd, int(c[:, :3].max()), n_batch)
+    read = H.table_invariants(table, c)
+    same = KS.kernel_map(cd, KS.KIND_SAME, s, table, n)
+    assert torch.equal(same.cpu().long(), oracle.nbr_same(c, s))
+    coarse = O.down_coords(c, s)
+    got_coarse = KS.downsample_coords(cd, s)
+    assert torch.equal(got_coarse.cpu().long(), coarse)
+    down = KS.kernel_map(got_coarse, KS.KIND_DOWN, s, table, n)
+    assert torch.equal(down.cpu().long(), oracle.nbr_down(c, coarse, s))
+    ctable = KS.hash_build(got_coarse, int(c[:, :3].max()), n_batch)
+    H.table_invariants(ctable, coarse)
+    up = KS.kernel_map(cd, KS.KIND_UP, s, ctable, len(coarse))
+    assert torch.equal(up.cpu().long(), oracle.nbr_up(c, coarse, s))
+    if extra is not None:
+        index = O._index(c)
+        q = torch.cat([c, extra])
+        qd = q.to(torch.int32).to(dev)
+        for kind, offs in ((KS.KIND_SAME, O.offsets3(s)), (KS.KIND_DOWN, O.offsets2(s))):
+            got = KS.kernel_map(qd, kind, s, table, n)
+            assert torch.equal(got.cpu().long(), O._lookup(index, q, offs))
+    return read, same
+
+
+@pytest.mark.parametrize("n,cap", list(zip(H.CAPACITY_NS, H.CAPACITIES)))
+def test_hash_at_the_capacity_boundaries(dev, n, cap):
+    """N = 512 rows fill half of 1024 slots, the highest load the table takes; row 513 doubles it."""
+    c = H.capacity_scene(n)
+    assert H.sp_capacity(n) == cap and int(KS.hash_build(c.to(torch.int32).to(dev), 64, 3).numel()) == cap + cap // 2
+    (keys, vals, disp, slots), same = _check_hash_scene(dev, c, 1, 3)
+    if n >= 511:
+        assert int((same >= 0).sum(1).median()) >= 3 and int(disp.max()) >= 1      # neighbours, and collisions, at all
+
+
+def test_hash_clustered_chain_wraps_the_table_end(dev):
+    """300 keys whose home slot is one of the last 8 of 1024: the chain wraps to slot 0 and runs on for hundreds of
+    slots, through the ordinary rows' home slots.  Queries for absent coordinates whose home slot lies in the chain walk
+    it to its end and find nothing."""
+    c, absent = H.clustered_scene()
+    (keys, vals, disp, slots), same = _check_hash_scene(dev, c, 1, 3, extra=absent)
+    home = H.sp_slot(keys[slots], H.CLUSTER_CAP)
+    wrapped = int((slots < home).sum())
+    print(f"clustered table: {wrapped} keys below their home slot, longest displacement {int(disp.max())}")
+    assert wrapped >= 250 and int(disp.max()) >= 250                  # the chain really wrapped, and is long
+    assert int(((same >= 0).sum(1) >= 2).sum()) >= 80
+
+
+def test_hash_duplicate_rows_the_last_wins_every_run(dev):
+    """Rows that repeat: one slot per coordinate, its value the largest row (atomicMax), whichever thread came first.  The
+    dictionary of the oracle has the same rule by construction: a later row overwrites an earlier one.  The table's bytes
+    are the same every run: the ordered insertion leaves one arrangement (with a first-come compare-and-swap two keys
+    of one home slot swapped places between runs, and this failed in one run of two on an MI355X)."""
+    c = H.duplicate_scene()
+    (keys, vals, disp, slots), same = _check_hash_scene(dev, c, 1, 2)
+    last = {}
+    for i, r in enumerate(map(tuple, c.tolist())):
+        last[r] = i
+    want = torch.tensor([last[tuple(r)] for r in c.tolist()])
+    assert int((want != torch.arange(len(c))).sum()) >= 100           # most rows are not the last of their coordinate
+    assert torch.equal(same[:, 13].cpu().long(), want)
+    cd = c.to(torch.int32).to(dev)
+    first = KS.hash_build(cd, 4, 2).cpu()
+    for _ in range(3):
+        assert torch.equal(KS.hash_build(cd, 4, 2).cpu(), first)      # the same table bytes every run
+
+
+@pytest.mark.parametrize("s", [1, 4])
+def test_hash_at_the_top_of_every_field(dev, s):
+    """The largest coordinate on every axis, the largest batch, and the largest key of all.  A +s step from a top voxel
+    is absent: not the voxel the sum would name if it carried into the next field of the key (H.top_scene puts one
+    there: the origin of the next cloud behind x, x + 1 behind y, y + 1 behind z).  No cloud follows MAX_BATCH."""
+    c = H.top_scene(s)
+    top = KS.MAX_COORD // s * s
+    (keys, vals, disp, slots), same = _check_hash_scene(dev, c, s, KS.MAX_BATCH + 1)
+    big = int(H.sp_key(torch.tensor([[top, top, top, KS.MAX_BATCH]]))[0])
+    assert big in keys.tolist() and int(keys[keys != H.EMPTY].max()) == big and big >> 62 == 1
+    cube = same.cpu().reshape(len(c), 3, 3, 3)                       # [row, iz, iy, ix]
+    want = O.nbr_same(c, s).reshape(len(c), 3, 3, 3)
+    n_top = 0
+    for axis, plane in ((0, (slice(None), slice(None), 2)), (1, (slice(None), 2)), (2, (2,))):
+        at = (c[:, axis] == top).nonzero()[:, 0]
+        n_top += len(at)
+        for i in at.tolist():
+            assert bool((cube[i][plane] == -1).all()) and bool((want[i][plane] == -1).all())
+            assert int(cube[i, 1, 1, 1]) == i
+    assert n_top >= 15
+    assert int((same >= 0).sum()) > len(c) + 10                      # the -s neighbours of the top voxels are found
+
+
+def test_hash_one_sweep(dev):
+    """30 000 rows in 65 536 slots.  The oracle is H.SortedOracle (tests/test_spconv_host.py pins it on the dictionary)."""
+    c = H.sweep_scene()
+    want = H.SortedOracle.nbr_same(c, 1)
+    assert int((want >= 0).sum(1).median()) >= 6                     # of 27, itself included
+    (keys, vals, disp, slots), same = _check_hash_scene(dev, c, 1, 2, oracle=H.SortedOracle)
+    assert len(keys) == 65536 and int(disp.max()) >= 4
+    print(f"one sweep: longest displacement {int(disp.max())}, mean {float(disp.mean()):.2f}")
+
+
 # ---- the convolution kernel -------------------------------------------------------------------------------------------
 def _conv_weights(K, Ci, Co, seed):
     """Mixed signs, output columns of very different scale (as tests/test_pointnet.py draws W3)."""
@@ -106,12 +217,26 @@ def _conv_table(M, n_in, K, transposed, seed):
     return torch.where(keep, nbr, torch.full_like(nbr, -1))
 
 
-CONV_CASES = [(4, 16, 27, False), (16, 16, 27, False), (16, 32, 1, False), (192, 128, 27, False), (64, 48, 27, False),
-              (48, 48, 8, False), (128, 128, 8, True)]
+CONV_CASES_EVERY_M = [(4, 16, 27, False), (16, 16, 27, False), (16, 32, 1, False), (192, 128, 27, False),
+                      (64, 48, 27, False), (48, 48, 8, False), (128, 128, 8, True)]
+# the other (Ci, Co, K) of the MinkUNet and the SPVCNN of O.CONFIG, at M = 1 and T + 1 (tests/test_spconv_host.py asserts
+# that CONV_CASES has every one): Co = 64 is an instance of the kernel of its own, Ci = 96 is staged as 64 + 32
+CONV_CASES_USED = [(16, 32, 27, False), (32, 32, 27, False), (32, 64, 27, False), (48, 48, 27, False), (64, 64, 27, False),
+                   (64, 128, 27, False), (96, 64, 27, False), (128, 128, 27, False),
+                   (16, 16, 8, False), (32, 32, 8, False), (64, 64, 8, False), (128, 128, 8, False),
+                   (128, 64, 8, True), (64, 48, 8, True), (48, 48, 8, True),
+                   (32, 64, 1, False), (64, 128, 1, False), (64, 48, 1, False), (96, 64, 1, False), (192, 128, 1, False)]
+CONV_CASES = CONV_CASES_EVERY_M + CONV_CASES_USED
+
+
+@pytest.mark.parametrize("M", [1, T + 1])
+@pytest.mark.parametrize("Ci,Co,K,transposed", CONV_CASES_USED)
+def test_conv_vs_float64_every_width_in_use(dev, Ci, Co, K, transposed, M):
+    test_conv_vs_float64(dev, Ci, Co, K, transposed, M)
 
 
 @pytest.mark.parametrize("M", [1, T - 1, T, T + 1, 2 * T + 3])
-@pytest.mark.parametrize("Ci,Co,K,transposed", CONV_CASES)
+@pytest.mark.parametrize("Ci,Co,K,transposed", CONV_CASES_EVERY_M)
 def test_conv_vs_float64(dev, Ci, Co, K, transposed, M):
     n_in = M if K == 1 else M + 5
     x = seeded_randn(n_in, Ci, seed=3 * M + Ci)
@@ -165,6 +290,63 @@ def test_centre_only_table_is_the_dense_product(dev):
     bad = nbr.clone()
     bad[0, 0], bad[1, 26] = n_in, -5
     assert torch.equal(KS.sparse_conv(xd, bad.to(torch.int32).to(dev), wd, bd), y27)
+
+
+def _structured_table(n_in, seed):
+    """[2 T + 3, 27]: which offsets a row has is decided by its wave and tile, so that the kernel's skipping of an offset
+    no row of the block has, and of one no row of the WAVE has while another wave has it, is at work in every tile.
+    Tile 0: wave w has only offsets with k % 4 == w.  Tile 1: offsets 0 .. 12 in its first 16 rows only, no offset at all
+    in the next 16, the centre alone in the third 16, nothing but k = 26 in the last 16.  The ragged tile 2: one row with
+    all 27 offsets, two with none."""
+    g = torch.Generator().manual_seed(seed)
+    M = 2 * T + 3
+    keep = torch.zeros((M, 27), dtype=torch.bool)
+    k = torch.arange(27)
+    for wv in range(4):
+        rows = slice(16 * wv, 16 * wv + 16)
+        keep[rows] = (torch.rand((16, 27), generator=g) < 0.6) & (k % 4 == wv)
+        keep[16 * wv] = k % 4 == wv                                   # one row of the wave has all of them
+    keep[T:T + 16] = (torch.rand((16, 27), generator=g) < 0.7) & (k <= 12)
+    keep[T] = k <= 12
+    keep[T + 32:T + 48, 13] = True
+    keep[T + 48:2 * T, 26] = True
+    keep[2 * T] = True
+    nbr = torch.randint(0, n_in, (M, 27), generator=g)
+    return torch.where(keep, nbr, torch.full_like(nbr, -1)), keep
+
+
+def test_structured_table_skipping_and_row_independence(dev):
+    M, Ci, Co, K = 2 * T + 3, 96, 64, 27
+    n_in = M + 5
+    nbr, keep = _structured_table(n_in, 5)
+    for wv in range(4):                                               # the table is what it says
+        has = keep[16 * wv:16 * wv + 16].any(0)
+        assert has.tolist() == [k % 4 == wv for k in range(27)]
+    assert keep[T:T + 16].any(0).tolist() == [k <= 12 for k in range(27)] and not bool(keep[T + 16:T + 32].any())
+    assert not bool(keep[T + 16:2 * T, :13].any()) and keep[T + 48:2 * T].sum(0).tolist() == [0] * 26 + [16]
+    assert bool(keep[2 * T].all()) and not bool(keep[2 * T + 1:].any())
+    x = seeded_randn(n_in, Ci, seed=41)
+    w, b = _conv_weights(K, Ci, Co, 42)
+    res = seeded_randn(M, Co, seed=43)
+    xd, wd, bd, resd, nd = x.to(dev), w.to(dev), b.to(dev), res.to(dev), nbr.to(torch.int32).to(dev)
+    # every wave of tile 0, two rows of tile 1, the row with all 27 offsets, a row with none
+    chosen = [0, 16, 37, 48, T + 5, 2 * T - 1, 2 * T, 2 * T + 1]
+    for with_res, relu in ((False, False), (True, True), (True, False)):
+        r = res if with_res else None
+        rd = resd if with_res else None
+        ref64 = O.conv(x.double(), nbr, w.double(), b.double(), None if r is None else r.double(), relu)
+        ref32 = O.conv(x, nbr, w, b, r, relu)
+        y = KS.sparse_conv(xd, nd, wd, bd, residual=rd, relu=relu)
+        _check_rows(y, ref32, ref64, f"structured table res={with_res} relu={relu}")
+        # rows without any offset: exactly act(b + res), nothing of x
+        plain = b[None].expand(M, Co) if r is None else b[None] + r
+        plain = torch.relu(plain) if relu else plain
+        empty = (~keep.any(1)).nonzero()[:, 0]
+        assert len(empty) == 18 and torch.equal(y.cpu()[empty], plain[empty])
+        # a row's bits depend on its own neighbours only: alone in a call of one row, the same bits
+        for j in chosen:
+            alone = KS.sparse_conv(xd, nd[j:j + 1], wd, bd, residual=None if rd is None else rd[j:j + 1], relu=relu)
+            assert torch.equal(alone[0], y[j]), (j, with_res, relu)
 
 
 # ---- the network ------------------------------------------------------------------------------------------------------

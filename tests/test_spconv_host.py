@@ -1,6 +1,8 @@
 """CPU tests of the Frechet Sparse Volume Distance: the float64 oracle (tests/_spconv_oracle.py) pinned on
 torch.nn.functional.conv3d / conv_transpose3d, the host-side pieces of the product (pcd2voxel, the model's state-dict
-names, the BatchNorm fold, build_model, the Frechet formula) and the argument checks of the C entry points."""
+names, the BatchNorm fold, build_model, the Frechet formula), the argument checks of the C entry points, and the host
+side of the GPU tests of the coordinate hash and the convolution widths (tests/_spconv_hash.py: the restated capacity, the
+scenes exist and are what they claim, the vectorised neighbour oracle is the dictionary's; CONV_CASES covers both models)."""
 import os
 import re
 import sys
@@ -11,6 +13,7 @@ import torch
 import torch.nn.functional as F
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import _spconv_hash as H  # noqa: E402
 import _spconv_oracle as O  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -368,3 +371,122 @@ def test_limits_and_widths_refuse_before_any_launch():
     for c in O.CONFIG["model_params"]["layer_num"]:
         assert int(0.5 * c) in KS.WIDTHS_OUT
     assert all(c in KS.WIDTHS_IN for c in (4, 192, 96, 64))
+
+
+# ---- the host side of the hash and width tests of tests/test_spconv.py ---------------------------------------------------
+def test_restated_capacity_is_the_librarys():
+    from lidarcrafter_amd import _lib
+
+    assert tuple(H.sp_capacity(n) for n in H.CAPACITY_NS) == H.CAPACITIES == (1024, 1024, 1024, 2048, 2048, 4096)
+    h = _lib.lib()
+    for n in H.CAPACITY_NS + (400, 30000, 32768, 32769):
+        assert h.lc_spconv_hash_bytes(n) == 12 * H.sp_capacity(n), n
+    assert H.sp_capacity(30000) == 65536
+    d = _defines()
+    assert (H.MAX_COORD, H.MAX_BATCH) == (d["LC_SPCONV_MAX_COORD"], d["LC_SPCONV_MAX_BATCH"])
+    # the largest key of all is not the empty marker, and every key is a non-negative int64
+    top = H.sp_key(np.array([[H.MAX_COORD, H.MAX_COORD, H.MAX_COORD, H.MAX_BATCH]]))
+    assert top[0] != H.EMPTY and int(top[0]) == (H.MAX_BATCH << 54) | ((1 << 54) - 1) and int(top[0]) >> 62 == 1
+    for n in H.CAPACITY_NS:
+        c = H.capacity_scene(n)
+        assert c.shape == (n, 4) and len({tuple(r) for r in c.tolist()}) == n and sorted(set(c[:, 3].tolist())) <= [0, 1, 2]
+    assert sorted(set(H.capacity_scene(513)[:, 3].tolist())) == [0, 1, 2]
+
+
+def test_clustered_scene_exists():
+    """300 keys of cloud 0 whose home slot is one of the last 8 of 1024, 100 ordinary rows, 50 absent coordinates whose
+    home slot lies in the chain those 300 must form."""
+    c, absent = H.clustered_scene()
+    assert c.shape == (400, 4) and absent.shape == (50, 4) and H.sp_capacity(len(c)) == H.CLUSTER_CAP
+    rows = {tuple(r) for r in c.tolist()}
+    assert len(rows) == 400 and not rows & {tuple(r) for r in absent.tolist()}
+    home = H.sp_slot(H.sp_key(c), H.CLUSTER_CAP)
+    assert int((home >= H.CLUSTER_CAP - 8).sum()) >= 300
+    ah = H.sp_slot(H.sp_key(absent), H.CLUSTER_CAP)
+    assert bool(((ah >= H.CLUSTER_CAP - 8) | (ah < 200)).all())
+    # a sequential insertion into 1024 slots: at least 292 of the 300 cannot stay in the last 8 slots
+    want = O.nbr_same(c, 1)
+    assert int(((want >= 0).sum(1) >= 2).sum()) >= 80                # the scene has neighbours
+    assert bool((O._lookup(O._index(c), absent, O.offsets3(1))[:, 13] == -1).all())
+
+
+def test_ordered_table_is_one_arrangement():
+    """What invariant (iv) of H.table_invariants compares a built table with: the same slots whatever the order of the
+    rows, every key behind smaller keys only, and the clustered keys wrapped over the end of the table."""
+    c, _ = H.clustered_scene()
+    keys, vals = H.ordered_table(c)
+    for seed in (1, 2):
+        perm = torch.randperm(len(c), generator=torch.Generator().manual_seed(seed))
+        k2, v2 = H.ordered_table(c[perm])
+        assert np.array_equal(k2, keys) and np.array_equal(perm.numpy()[v2[v2 >= 0]], vals[vals >= 0])
+    disp, slots = H.displacements(keys, H.CLUSTER_CAP)
+    assert len(slots) == 400 and int((slots < H.sp_slot(keys[slots], H.CLUSTER_CAP)).sum()) >= 250 and int(disp.max()) >= 250
+    for h, d in zip(slots.tolist(), disp.tolist()):
+        between = keys[(h - np.arange(1, d + 1)) % H.CLUSTER_CAP]
+        assert bool((between < keys[h]).all())
+    d = H.duplicate_scene()
+    kd, vd = H.ordered_table(d)
+    last = {tuple(r): i for i, r in enumerate(d.tolist())}
+    assert int((kd != H.EMPTY).sum()) == 104 and sorted(vd[vd >= 0].tolist()) == sorted(last.values())
+
+
+def test_scenes_are_what_they_claim():
+    d = H.duplicate_scene()
+    rows = {}
+    for r in map(tuple, d.tolist()):
+        rows[r] = rows.get(r, 0) + 1
+    times = sorted(rows.values())
+    assert len(rows) == 104 and times.count(1) == 40 and sorted(set(times)) == [1, 2, 3, 4, 5] and len(d) == 40 + 16 * 14
+    for s in (1, 4):
+        t = H.top_scene(s)
+        top = H.MAX_COORD // s * s
+        assert len({tuple(r) for r in t.tolist()}) == len(t) and int(t[:, :3].max()) == top and top + s == 1 << 18
+        assert [top, top, top, H.MAX_BATCH] in t.tolist() and [top, top, top, H.MAX_BATCH - 1] in t.tolist()
+        for axis in range(3):
+            assert int((t[:, axis] == top).sum()) >= 5
+        for x, y, z, b in t.tolist():                                # behind every top voxel: the origin of the next cloud
+            if top in (x, y, z) and b < H.MAX_BATCH:
+                assert [0, 0, 0, b + 1] in t.tolist()
+    w = H.sweep_scene()
+    assert w.shape == (30000, 4) and len(np.unique(H.sp_key(w))) == 30000 and H.sp_capacity(len(w)) == 65536
+    assert sorted(set(w[:, 3].tolist())) == [0, 1]
+
+
+@pytest.mark.parametrize("s", [1, 2, 4])
+def test_sorted_oracle_is_the_dictionary_oracle(s):
+    """The searchsorted oracle the 30 000-row scene is checked by, against O.nbr_* at 500 rows, on the rows at the top of
+    every field and on rows that repeat (the last one wins in both)."""
+    scenes = [H.capacity_scene(500) * torch.tensor([s, s, s, 1]), H.duplicate_scene() * torch.tensor([s, s, s, 1])]
+    if s in (1, 4):
+        scenes.append(H.top_scene(s))
+    for c in scenes:
+        coarse = O.down_coords(c, s)
+        assert torch.equal(H.SortedOracle.nbr_same(c, s), O.nbr_same(c, s))
+        assert torch.equal(H.SortedOracle.nbr_down(c, coarse, s), O.nbr_down(c, coarse, s))
+        assert torch.equal(H.SortedOracle.nbr_up(c, coarse, s), O.nbr_up(c, coarse, s))
+    assert int((O.nbr_same(scenes[0], s) >= 0).sum()) > 3 * 500
+
+
+def _kernel_shapes(model):
+    """{(Ci, Co, K, transposed)} of every `.kernel` of the model: ks 1 kernels have no offset axis; the transposed
+    convolutions are the first of every up stage."""
+    out = set()
+    for k, v in model.state_dict().items():
+        if k.endswith(".kernel"):
+            transposed = bool(re.fullmatch(r"up\d\.0\.net\.0\.kernel", k))
+            out.add((v.shape[-2], v.shape[-1], v.shape[0] if v.dim() == 3 else 1, transposed))
+    return out
+
+
+def test_conv_cases_cover_every_width_of_both_models():
+    import test_spconv as TS
+    from lidargen.metrics.models.spvcnn.model import Model as SPVCNN
+
+    used = _kernel_shapes(_model()) | _kernel_shapes(SPVCNN(O.CONFIG))
+    assert len(used) == 25 and (96, 64, 27, False) in used and (128, 64, 8, True) in used
+    cases = set(TS.CONV_CASES)
+    assert len(cases) == len(TS.CONV_CASES)
+    for Ci, Co, K, transposed in sorted(used):
+        assert (Ci, Co, K, transposed) in cases, (Ci, Co, K, transposed)
+    assert any(K == 27 and Co == 64 for _, Co, K, _ in cases) and any(K == 27 and Ci == 96 for Ci, _, K, _ in cases)
+    assert {Co // 16 for _, Co, _, _ in cases} == {1, 2, 3, 4, 8}    # every instance of the kernel

@@ -14,6 +14,7 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import _spconv_hash as H  # noqa: E402
 import _spconv_oracle as O  # noqa: E402
 import _spvcnn_oracle as PV  # noqa: E402
 
@@ -116,6 +117,43 @@ def test_query_equals_the_oracle(dev, s):
     assert no_w is None and torch.equal(only_idx, idx)
     again, w_again = KV.query(pts.to(dev), s, table, len(c))
     assert torch.equal(again, idx) and torch.equal(w_again, w)
+
+
+def _hash_scenes():
+    c, _ = H.clustered_scene()
+    nb = KS.MAX_BATCH + 1
+    return {"clustered": (c, 1, 3), "top-1": (H.top_scene(1), 1, nb), "top-4": (H.top_scene(4), 4, nb)}
+
+
+@pytest.mark.parametrize("scene", ["clustered", "top-1", "top-4"])
+def test_query_on_the_hash_scenes(dev, scene):
+    """The query's own probe loop on the tables of tests/_spconv_hash.py: a chain of 300 keys that wraps the end of the
+    table, and voxels at the largest coordinate of every axis and in the largest batch (the probes at + s beyond them
+    are absent, not the voxel a carry into the next field of the key would name).  Points as in `_scene_points`."""
+    c, s, n_batch = _hash_scenes()[scene]
+    pts = _scene_points(c, s)
+    want_idx, w64 = PV.point_maps(pts, c, s, torch.float64)
+    _, w32 = PV.point_maps(pts, c, s, torch.float32)
+    n_nbr = (want_idx >= 0).sum(1)
+    assert int(n_nbr.max()) >= 2 and int(n_nbr.min()) == 0 and int((n_nbr > 0).sum()) >= 2 * len(c)
+    cd = c.to(torch.int32).to(dev)
+    table = KS.hash_build(cd, int(c[:, :3].max()), n_batch)
+    keys, vals, disp, slots = H.table_invariants(table, c)
+    if scene == "clustered":
+        assert int((slots < H.sp_slot(keys[slots], H.CLUSTER_CAP)).sum()) >= 250 and int(disp.max()) >= 250
+    idx, w = KV.query(pts.to(dev), s, table, len(c))
+    assert torch.equal(idx.cpu().long(), want_idx)
+    base = torch.cat([(torch.floor(pts[:, :3] / s) * s), pts[:, 3:]], 1).to(torch.int32).to(dev)
+    assert torch.equal(idx, KS.kernel_map(base, KS.KIND_DOWN, s, table, len(c)))
+    _check_rows(w, w32, w64, f"trilinear weights on the {scene} table")
+    assert bool((w.cpu()[n_nbr == 0] == 0).all()) and bool(torch.isfinite(w).all())
+    if scene != "clustered":                                         # on a top voxel: no probe beyond it finds anything
+        top = KS.MAX_COORD // s * s
+        on = pts[:len(c)]
+        for axis, ks in ((0, [4, 5, 6, 7]), (1, [2, 3, 6, 7]), (2, [1, 3, 5, 7])):
+            at = (on[:, axis] == top).nonzero()[:, 0]
+            got = idx.cpu()[at]
+            assert len(at) >= 5 and bool((got[:, ks] == -1).all()) and bool((got[:, 0] == at).all())
 
 
 # ---- devoxelize -------------------------------------------------------------------------------------------------------
