@@ -61,6 +61,23 @@ __device__ __forceinline__ void lc_st4(__amdgpu_buffer_rsrc_t rs, unsigned byte_
 // GroupNorm apply passes, which are VALU-bound, not HBM-bound (profiles/r05_level0.txt section 7).
 __device__ __forceinline__ float lc_silu(float v) { return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v)); }
 
+// A lane's float as a wave-uniform value.  __builtin_amdgcn_readlane / readfirstlane take and return `int`: handed a
+// float they CONVERT it, and the "pivot" of a statistics entry came back truncated to an integer -- up to 1 away from
+// every value it was meant to sit among (tests/test_gn_structured.py).  The bits go through unchanged here.
+__device__ __forceinline__ float lc_readlane_f32(float v, int lane) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), lane));
+}
+__device__ __forceinline__ float lc_readfirstlane_f32(float v) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
+}
+
+// lanes 0-31: lo, lanes 32-63: hi (both wave-uniform).  Bit arithmetic, not a select: hipcc turns selects in the
+// convolutions' deferred epilogues into exec-mask branches inside the MFMA stream.
+__device__ __forceinline__ float lc_half_select(float lo, float hi) {
+    const unsigned m = (unsigned)((int)(threadIdx.x << 26) >> 31);
+    return __uint_as_float((__float_as_uint(lo) & ~m) | (__float_as_uint(hi) & m));
+}
+
 __device__ __forceinline__ double lc_wave_sum(double v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

@@ -277,7 +277,7 @@ __global__ __launch_bounds__(256, (C::BN > 64 && C::NTAP == 9) ? 1 : 2) void con
                 if constexpr (EMIT) {      // per channel octet (m; both lane halves) of this wave's pixels, as the pipelined kernels
                     const int m = r >> 2;
                     if (j == 0 && (r & 3) == 0) {
-                        st_p[i][m] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, pok ? v : 0.0f), 0));
+                        st_p[i][m] = lc_readlane_f32(pok ? v : 0.0f, 0);
                         st_s[i][m] = 0.f; st_q[i][m] = 0.f;
                     }
                     const float d = pok ? v - st_p[i][m] : 0.0f;
@@ -1405,7 +1405,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
         if (ok[k]) y[b * y_bs + (long long)(c0 + k) * HW + p] = v[k];
     }
     if (ostats) {                                  // Co % 8 == 0 (checked by the launcher)
-        const float piv = __builtin_amdgcn_readfirstlane(v[0]);
+        const float piv = lc_readfirstlane_f32(v[0]);
         float s_ = 0.f, q_ = 0.f;
 #pragma unroll
         for (int k = 0; k < 8; ++k) {

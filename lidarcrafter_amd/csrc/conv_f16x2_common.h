@@ -421,6 +421,11 @@ struct DefEpi {                // branch here split the MFMAs' basic block -- le
     float rq[RING];
     float st_p, st_s, st_q;    // the running octet: pivot, sum (v - p), sum (v - p)^2 of channels q = 0, 1 of each quad
     float st_s2, st_q2;        // pair entries: ... and of channels q = 2, 3 (unused for octet entries)
+    // Pair entries: every entry has a pivot of ITS OWN channels -- st_p is then per lane (lanes 0-31: lane 0's first
+    // value of q = 0, lanes 32-63: lane 32's), st_p2 the same for q = 2, 3.  With the octet's one pivot a pair whose level
+    // sits D away from the octet's first channel summed d ~ D in float32 and lost (D / std)^2 ulps of its variance
+    // (GroupNorm32 on channels at different levels: tests/test_gn_structured.py).
+    float st_p2;
     static constexpr bool pairs = EMIT == 2;   // entries per channel pair (ConvArgsH::ounit == 2)
     unsigned voff[TPX];        // byte offset of (channel co_wave, pixel j) in the sample; OOB = nothing to do
     __amdgpu_buffer_rsrc_t rs_y, rs_r, rs_o;
@@ -445,6 +450,7 @@ struct DefEpi {                // branch here split the MFMAs' basic block -- le
         oct_stride = (unsigned)oslots * 16u;
         nv8 = 0.f; ent_off = OOB;
         st_p = st_s = st_q = st_s2 = st_q2 = 0.f;
+        st_p2 = 0.f;
 #pragma unroll
         for (int j = 0; j < TPX; ++j) voff[j] = OOB;
 #pragma unroll
@@ -470,6 +476,13 @@ struct DefEpi {                // branch here split the MFMAs' basic block -- le
         rq[k % RING] = __builtin_bit_cast(
             float, __builtin_amdgcn_raw_buffer_load_b32(rs_r, off_of(k), (unsigned)cor_of(k) * HW4, 0));
     }
+    // the pivot of an entry: lane 0's value for the whole wave (octet entries), or lane 0's for lanes 0-31 and lane 32's
+    // for lanes 32-63 (pair entries: one entry per half-wave)
+    static __device__ __forceinline__ float half_pivot(float v) {
+        const float lo = lc_readlane_f32(v, 0);
+        if constexpr (!pairs) return lo;
+        else return lc_half_select(lo, lc_readlane_f32(v, 32));
+    }
     __device__ __forceinline__ void finalize(int k) { finalize_with(k, rq[k % RING]); }
     __device__ __forceinline__ void finalize_with(int k, float res) {
         const int i = i_of(k), m = m_of(k), j = j_of(k), r = 4 * m + (k & 3);
@@ -483,11 +496,12 @@ struct DefEpi {                // branch here split the MFMAs' basic block -- le
         if constexpr (EMIT) {
             const bool pok = voff[j] != OOB;
             if (k % OCTV == 0) {
-                st_p = __builtin_amdgcn_readlane(pok ? v : 0.0f, 0);
+                st_p = half_pivot(pok ? v : 0.0f);
                 st_s = 0.f; st_q = 0.f; st_s2 = 0.f; st_q2 = 0.f;
             }
-            const float d = pok ? v - st_p : 0.0f;
-            if (pairs && (k & 2)) { st_s2 += d; st_q2 = fmaf(d, d, st_q2); }   // (k & 3 = channel inside the lane's quad)
+            if (pairs && k % OCTV == 2) st_p2 = half_pivot(pok ? v : 0.0f);      // first value of channels q = 2, 3
+            const float d = pok ? v - ((pairs && (k & 2)) ? st_p2 : st_p) : 0.0f;    // (k & 3 = channel inside the lane's quad)
+            if (pairs && (k & 2)) { st_s2 += d; st_q2 = fmaf(d, d, st_q2); }
             else { st_s += d; st_q = fmaf(d, d, st_q); }
             if (k % OCTV == OCTV - 1) {                  // the octet is complete
                 const int oct = i * 4 + m;               // octet index inside this wave's channel rows
@@ -508,7 +522,7 @@ struct DefEpi {                // branch here split the MFMAs' basic block -- le
                 } else {                                 // pairs (8m + 4kh + 0,1) and (+ 2,3) from lanes 31 / 63
                     store_entry_lanes(st_p, nv8, half_sum_to_lane31_63(st_s), half_sum_to_lane31_63(st_q), vo,
                                   (unsigned)(4 * oct) * oct_stride);
-                    store_entry_lanes(st_p, nv8, half_sum_to_lane31_63(st_s2), half_sum_to_lane31_63(st_q2), vo,
+                    store_entry_lanes(st_p2, nv8, half_sum_to_lane31_63(st_s2), half_sum_to_lane31_63(st_q2), vo,
                                   (unsigned)(4 * oct + 1) * oct_stride);
                 }
             }

@@ -310,14 +310,21 @@ __global__ __launch_bounds__(512, 1) void conv_f16x2_pp_kernel(ConvArgsH a) {
         // scratch access in a stage slot is a vmcnt(0) that drains the loads just issued)
         asm volatile("; epilogue octet %0" ::"n"(m));
         float st_p = 0.f, st_s = 0.f, st_q = 0.f, st_s2 = 0.f, st_q2 = 0.f;
+        float st_p2 = 0.f;      // pair entries: st_p / st_p2 are per lane, a pivot of each entry's own channels (DefEpi)
+        auto half_pivot = [&](float v) __attribute__((always_inline)) {
+            const float lo = lc_readlane_f32(v, 0);
+            if constexpr (!pairs) return lo;
+            else return lc_half_select(lo, lc_readlane_f32(v, 32));
+        };
 #pragma unroll
         for (int k = 0; k < 4 * TPX; ++k) {
             const int j = k >> 2, q = k & 3;
             const float v = fmaf(accp[j][4 * m + q], out_unscale, res[k]) * out_scale;
             ov[k] = v;
             if constexpr (EMIT != 0) {
-                if (k == 0) st_p = __builtin_amdgcn_readlane(v, 0);
-                const float d = v - st_p;
+                if (k == 0) st_p = half_pivot(v);
+                if (pairs && k == 2) st_p2 = half_pivot(v);
+                const float d = v - ((pairs && (q & 2)) ? st_p2 : st_p);
                 if (pairs && (q & 2)) { st_s2 += d; st_q2 = fmaf(d, d, st_q2); }
                 else { st_s += d; st_q = fmaf(d, d, st_q); }
             }
@@ -334,7 +341,7 @@ __global__ __launch_bounds__(512, 1) void conv_f16x2_pp_kernel(ConvArgsH a) {
                 ev[0] = entry(st_p, 8.0f * 32.0f * TPX, wave_sum_to_lane63(st_s), wave_sum_to_lane63(st_q));
             } else {
                 ev[0] = entry(st_p, 2.0f * 32.0f * TPX, half_sum_to_lane31_63(st_s), half_sum_to_lane31_63(st_q));
-                ev[1] = entry(st_p, 2.0f * 32.0f * TPX, half_sum_to_lane31_63(st_s2), half_sum_to_lane31_63(st_q2));
+                ev[1] = entry(st_p2, 2.0f * 32.0f * TPX, half_sum_to_lane31_63(st_s2), half_sum_to_lane31_63(st_q2));
             }
         }
     };

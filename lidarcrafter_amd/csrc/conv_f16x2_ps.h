@@ -324,7 +324,9 @@ __global__ __launch_bounds__(C::NT, C::NT / 256) void conv_f16x2_ps_kernel(ConvA
             continue;
         }
         // ---- epilogue: as conv_f16x2_pipe_kernel --------------------------------------------
-        float st_p[C::TCO_][4], st_s[C::TCO_][4], st_q[C::TCO_][4];
+        // (st_ph: quad entries -- the upper half-wave's quad 8m+4 .. 8m+7 has a pivot of its own channels; not used for octets)
+        float st_p[C::TCO_][4], st_ph[C::TCO_][4], st_s[C::TCO_][4], st_q[C::TCO_][4];
+        const bool upper_quad = a.ounit == 4 && (lane & 32);
         int nvalid = 0;
 #pragma unroll
         for (int j = 0; j < C::TPX_; ++j) {
@@ -351,10 +353,11 @@ __global__ __launch_bounds__(C::NT, C::NT / 256) void conv_f16x2_ps_kernel(ConvA
                     if constexpr (EMIT_STATS && !(LC_EMIT_ABL & 1)) {
                         const int m = r >> 2;
                         if (j == 0 && (r & 3) == 0) {
-                            st_p[i][m] = __builtin_amdgcn_readlane(pok ? v : 0.0f, 0);
+                            st_p[i][m] = lc_readlane_f32(pok ? v : 0.0f, 0);
+                            st_ph[i][m] = lc_readlane_f32(pok ? v : 0.0f, 32);
                             st_s[i][m] = 0.f; st_q[i][m] = 0.f;
                         }
-                        const float d = pok ? v - st_p[i][m] : 0.0f;
+                        const float d = pok ? v - (upper_quad ? st_ph[i][m] : st_p[i][m]) : 0.0f;
                         st_s[i][m] += d;
                         st_q[i][m] = fmaf(d, d, st_q[i][m]);
                     }
@@ -368,7 +371,7 @@ __global__ __launch_bounds__(C::NT, C::NT / 256) void conv_f16x2_ps_kernel(ConvA
             // each, i.e. every entry waited for all of the tile's output stores: +6 ... +11 us per launch,
             // profiles/r05_level0.txt section 7).  Octet entries: lane 63 holds the sums; quad entries (a consumer
             // GroupNorm with 4 / 12 channels per group): lanes 0-31 hold channels 8m .. 8m+3, lanes 32-63 8m+4 .. 8m+7
-            // -- the two half-wave sums in lanes 31 / 63, one pivot.
+            // -- the two half-wave sums in lanes 31 / 63, each around a pivot of its own quad (lanes 0 / 32).
             const int slot = ((h0 / C::TH_) * a.tiles_w + w0 / C::TW_) * C::WPX_ + wpx;
             const int co_blk = co0 + wco * C::TCO_ * 32;
             const bool quads = a.ounit == 4;
@@ -389,7 +392,7 @@ __global__ __launch_bounds__(C::NT, C::NT / 256) void conv_f16x2_ps_kernel(ConvA
                     const unsigned vo = (mine && co_oct < a.Co)
                                             ? ((unsigned)ent * (unsigned)a.oslots + (unsigned)slot) * 16u + 4u * (lane & 3)
                                             : 0x80000000u;
-                    store_entry_4lanes(rs_o, st_p[i][m], nv, quads ? sh : sf, quads ? qh : qf, vo);
+                    store_entry_4lanes(rs_o, upper_quad ? st_ph[i][m] : st_p[i][m], nv, quads ? sh : sf, quads ? qh : qf, vo);
                 }
             }
         }

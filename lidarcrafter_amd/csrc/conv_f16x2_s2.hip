@@ -331,7 +331,8 @@ __global__ __launch_bounds__(256, 1) void conv_s2_shared_w_kernel(ConvArgsH a) {
         const bool pok = gh < H && gw < W;
         const unsigned vo = pok ? (unsigned)(co_wave * HW + gh * W + gw) * 4u : OOB;
         const float brow = (gh == 0 ? 0.875f : 1.0f) + (gh == H - 1 ? 0.875f : 1.0f) - 1.0f;
-        float st_p[4], st_s[4], st_q[4];
+        float st_p[4], st_ph[4], st_s[4], st_q[4];      // (st_ph: the upper half-wave's quad has a pivot of its own channels)
+        const bool upper_quad = quads && (lane & 32);
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int cor = (r & 3) + 8 * (r >> 2);
@@ -340,8 +341,11 @@ __global__ __launch_bounds__(256, 1) void conv_s2_shared_w_kernel(ConvArgsH a) {
                                                   (unsigned)cor * HW4, LC_DEF_AUX);
             if constexpr (EMIT_STATS) {
                 const int m = r >> 2;
-                if ((r & 3) == 0) { st_p[m] = __builtin_amdgcn_readlane(pok ? v : 0.0f, 0); st_s[m] = 0.f; st_q[m] = 0.f; }
-                const float d = pok ? v - st_p[m] : 0.0f;
+                if ((r & 3) == 0) {
+                    st_p[m] = lc_readlane_f32(pok ? v : 0.0f, 0); st_ph[m] = lc_readlane_f32(pok ? v : 0.0f, 32);
+                    st_s[m] = 0.f; st_q[m] = 0.f;
+                }
+                const float d = pok ? v - (upper_quad ? st_ph[m] : st_p[m]) : 0.0f;
                 st_s[m] += d;
                 st_q[m] = fmaf(d, d, st_q[m]);
             }
@@ -360,7 +364,7 @@ __global__ __launch_bounds__(256, 1) void conv_s2_shared_w_kernel(ConvArgsH a) {
                 const unsigned eo = (mine && co_oct < a.Co && gh < H)
                                         ? ((unsigned)ent * (unsigned)a.oslots + (unsigned)slot) * 16u + 4u * (lane & 3)
                                         : OOB;
-                store_entry_4lanes(rs_o, st_p[m], nv, quads ? sh : sf, quads ? qh : qf, eo);
+                store_entry_4lanes(rs_o, upper_quad ? st_ph[m] : st_p[m], nv, quads ? sh : sf, quads ? qh : qf, eo);
             }
         }
     }

@@ -128,7 +128,7 @@ __global__ __launch_bounds__(256) void down2_vec_kernel(const float* __restrict_
             lc_st2(y2b + ((long long)c * Ho + i) * Wo + w0 / 2, o2);
         }
         if (ostats) {                                          // (uniform)
-            const float piv = __builtin_amdgcn_readfirstlane(acc0);
+            const float piv = lc_readfirstlane_f32(acc0);
             const float d0 = acc0 - piv, d1 = acc1 - piv;
             float s_ = d0 + d1, q_ = fmaf(d1, d1, d0 * d0);
 #pragma unroll

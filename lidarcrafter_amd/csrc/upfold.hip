@@ -210,7 +210,10 @@ __global__ __launch_bounds__(256) void up2_combine9_kernel(const float* __restri
             lc_st4(rs_y2, off + row_bytes, xb2);
         }
         if (STATS) {
-            const float piv = __builtin_amdgcn_readfirstlane(top[0]);
+            // (the next rows' loads stay in front of the 16-byte stores above, where the source has them: sunk behind the
+            //  stores, one of them wrote a data register of the store right in front of it -- devtools/isa_store_audit.py)
+            __builtin_amdgcn_sched_barrier(0);
+            const float piv = lc_readfirstlane_f32(top[0]);
             float s_ = 0.0f, q_ = 0.0f;
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
