@@ -169,7 +169,7 @@ __global__ __launch_bounds__(256, (C::BN > 64 && C::NTAP == 9) ? 1 : 2) void con
     if (a.gn) {
         if (a.gs.partials) {
             for (int i = tid; i < a.Cgn; i += 256) ctab[i] = gn_row_from_stats(a.gs, xb, b, i, a.Ci, HW);
-        } else if (a.seg[0].p) {
+        } else if (a.segs.seg[0].p) {
             gn_rows_from_ostats<256>(a, b, tid, ctab, gtab);
         } else {
             const f32x4* g = a.gn + (long long)b * a.Cgn;
@@ -244,7 +244,7 @@ __global__ __launch_bounds__(256, (C::BN > 64 && C::NTAP == 9) ? 1 : 2) void con
             const int co = co_wave + i * 32 + (r & 3) + 8 * (r >> 2);
             bias_r[i][r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_b, (unsigned)co * 4u, 0, 0));
         }
-    float st_p[C::TCO_][4], st_s[C::TCO_][4], st_q[C::TCO_][4];
+    StatAcc<PIVOT_WAVE> st[C::TCO_][4];
     int nvalid = 0;
 #pragma unroll
     for (int j = 0; j < C::TPX_; ++j) {
@@ -276,13 +276,8 @@ __global__ __launch_bounds__(256, (C::BN > 64 && C::NTAP == 9) ? 1 : 2) void con
                                                       co_wave + cor < a.Co ? vo : OOB, (unsigned)cor * HW4, LC_NP_AUX);
                 if constexpr (EMIT) {      // per channel octet (m; both lane halves) of this wave's pixels, as the pipelined kernels
                     const int m = r >> 2;
-                    if (j == 0 && (r & 3) == 0) {
-                        st_p[i][m] = lc_readlane_f32(pok ? v : 0.0f, 0);
-                        st_s[i][m] = 0.f; st_q[i][m] = 0.f;
-                    }
-                    const float d = pok ? v - st_p[i][m] : 0.0f;
-                    st_s[i][m] += d;
-                    st_q[i][m] = fmaf(d, d, st_q[i][m]);
+                    if (j == 0 && (r & 3) == 0) st[i][m].start(pok ? v : 0.0f);
+                    st[i][m].add(v, pok);
                 }
             }
         }
@@ -299,11 +294,11 @@ __global__ __launch_bounds__(256, (C::BN > 64 && C::NTAP == 9) ? 1 : 2) void con
 #pragma unroll
             for (int m = 0; m < 4; ++m) {
                 const int co_oct = co_blk + i * 32 + 8 * m;
-                const float sf = wave_sum_to_lane63(st_s[i][m]), qf = wave_sum_to_lane63(st_q[i][m]);
+                const float sf = wave_sum_to_lane63(st[i][m].s), qf = wave_sum_to_lane63(st[i][m].q);
                 const unsigned vo = (lane >= 60 && co_oct < a.Co)
                                         ? ((unsigned)(co_oct >> 3) * (unsigned)a.oslots + (unsigned)slot) * 16u + 4u * (lane & 3)
                                         : OOB;
-                store_entry_4lanes(rs_o, st_p[i][m], nv, sf, qf, vo);
+                store_entry_4lanes(rs_o, st[i][m].p, nv, sf, qf, vo);
             }
     }
 }
@@ -653,7 +648,7 @@ __global__ __launch_bounds__(C::NT, C::NT / 256) void conv_f16x2_pipe_kernel(Con
     if constexpr (GNM != 0) {   // rows of the fused input norm, derived while the chunk-0 loads are in flight
         if (a.gs.partials) {
             for (int i = tid; i < a.Cgn; i += NT) ctab[i] = gn_row_from_stats(a.gs, xb, b, i, a.Ci, HW);
-        } else if (a.seg[0].p) {
+        } else if (a.segs.seg[0].p) {
             gn_rows_from_ostats<NT>(a, b, tid, ctab, gtab);
         } else {
             const f32x4* g = a.gn + (long long)b * a.Cgn;
@@ -1246,22 +1241,14 @@ extern "C" int lc_conv2d_ring_f16x2_fwd(const float* x, int64_t x_bs, const void
     a.gn = reinterpret_cast<const f32x4*>(gn_coeffs);
     a.Cgn = gn_cpad; a.gn_silu = gn_silu;
     a.gs = lc_gn_stats_input{nullptr, 0, 0, 0.f, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr};
-    a.seg[0] = a.seg[1] = ConvArgsH::OctSeg{nullptr, 0, 0, 3};
+    a.segs = STAT_SEGS_NONE;
     if (gn_stats) {
         if (gn_coeffs || gn_stats->G <= 0 || Ci % gn_stats->G) return LC_EINVAL;
         if (gn_stats->partials) {
             if (gn_stats->nch <= 0) return LC_EINVAL;
         } else {
-            const lc_oct_stats *s0 = gn_stats->os0, *s1 = gn_stats->os1;
-            if (!s0 || !s0->p || s0->channels <= 0 || s0->slots <= 0) return LC_EINVAL;
-            if (s1 && (!s1->p || s1->channels <= 0 || s1->slots <= 0)) return LC_EINVAL;
-            const int c0 = s0->channels, c1 = s1 ? s1->channels : 0, cpg = Ci / gn_stats->G;
-            const int u0 = s0->unit, u1 = s1 ? s1->unit : u0;
-            auto ush_of = [](int u) { return u == 8 ? 3 : (u == 4 ? 2 : (u == 2 ? 1 : (u == 1 ? 0 : -1))); };
-            if (ush_of(u0) < 0 || ush_of(u1) < 0) return LC_EINVAL;      // entries per octet / quad / pair / channel
-            if (c0 + c1 != Ci || cpg % u0 || cpg % u1 || c0 % cpg || gn_stats->G > GN_MAX_G) return LC_EUNSUP;
-            a.seg[0] = ConvArgsH::OctSeg{reinterpret_cast<const f32x4*>(s0->p), c0, s0->slots, ush_of(u0)};
-            if (s1) a.seg[1] = ConvArgsH::OctSeg{reinterpret_cast<const f32x4*>(s1->p), c1, s1->slots, ush_of(u1)};
+            if (const int rc = stat_segs_from(gn_stats->os0, gn_stats->os1, Ci, Ci / gn_stats->G, LC_EINVAL, a.segs)) return rc;
+            if (gn_stats->G > GN_MAX_G) return LC_EUNSUP;
         }
         a.gs = *gn_stats;
         a.gs.os0 = a.gs.os1 = nullptr;
@@ -1336,7 +1323,7 @@ extern "C" int lc_conv2d_ring_f16x2_ps_fwd(const void* x_split, const void* wp_h
     a.tiles_h = a.tiles_w = 0;
     a.gn = nullptr; a.Cgn = 0; a.gn_silu = 0;
     a.gs = lc_gn_stats_input{nullptr, 0, 0, 0.f, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr};
-    a.seg[0] = a.seg[1] = ConvArgsH::OctSeg{nullptr, 0, 0, 3};
+    a.segs = STAT_SEGS_NONE;
     a.tpb = 0;
     if (tile_cfg >= 100) { a.tpb = tile_cfg / 100; tile_cfg %= 100; }
     // (the pipelined tile shapes only: the heuristic's Ci >= 24 branch)
@@ -1405,20 +1392,16 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
         if (ok[k]) y[b * y_bs + (long long)(c0 + k) * HW + p] = v[k];
     }
     if (ostats) {                                  // Co % 8 == 0 (checked by the launcher)
-        const float piv = lc_readfirstlane_f32(v[0]);
-        float s_ = 0.f, q_ = 0.f;
+        StatAcc<PIVOT_FIRST> st;
+        st.start(v[0]);
 #pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const float d = pok ? v[k] - piv : 0.0f;
-            s_ += d; q_ = fmaf(d, d, q_);
-        }
+        for (int k = 0; k < 8; ++k) st.add(v[k], pok);
         const int nvalid = __popcll(__ballot(pok));
-        s_ = wave_sum_to_lane63(s_);
-        q_ = wave_sum_to_lane63(q_);
+        const float s_ = wave_sum_to_lane63(st.s), q_ = wave_sum_to_lane63(st.q);
         const int slot = blockIdx.x * 4 + (threadIdx.x >> 6);
         if ((threadIdx.x & 63) == 63 && slot < oslots)
             ostats[((long long)b * (Co >> 3) + oct) * oslots + slot] =
-                f32x4{piv, (float)(8 * nvalid), s_, q_};
+                f32x4{st.p, (float)(8 * nvalid), s_, q_};
     }
 }
 }  // namespace

@@ -1,11 +1,13 @@
 // Shared pieces of the f16x2 convolution kernels (conv_f16x2.hip, conv_f16x2_tall.hip): argument block, tile
-// configuration, THE split rule, fused-GroupNorm row derivation, DPP sums, LDS-DMA and wait helpers.
+// configuration, THE split rule, fused-GroupNorm row derivation, LDS-DMA and wait helpers, the deferred epilogue.
+// The GroupNorm statistics entries the epilogues write and the prologues fold: stats_entry.h.
 // See the header comment of conv_f16x2.hip for the arithmetic.
 #pragma once
 #include <cstdlib>
 #include <type_traits>
 
 #include "common.h"
+#include "stats_entry.h"
 
 #ifndef LC_EPI_MODE
 #define LC_EPI_MODE 2   // 0 plain stores, 2 write-through (sc1) stores (developer A/B)
@@ -95,19 +97,15 @@ struct ConvArgsH {
     int Cgn, gn_silu;
     // ... or the statistics themselves (lc_groupnorm_stats partials): the block derives the rows of
     // its sample in its prologue, so no lc_groupnorm_coeffs launch sits between stats and conv
-    lc_gn_stats_input gs;     // (os0 / os1 are host pointers: the kernels read seg[] instead)
-    // ... or the octet statistics the input's producer(s) emitted (gs.partials == NULL):
-    // seg[0] covers channels [0, seg[0].channels), seg[1] the rest
-    struct OctSeg { const f32x4* p; int channels, slots, ush; } seg[2];   // ush: log2(channels per entry) = 3, 2, 1 or 0
+    lc_gn_stats_input gs;     // (os0 / os1 are host pointers: the kernels read segs instead)
+    // ... or the statistics entries the input's producer(s) emitted (gs.partials == NULL)
+    StatSegs segs;
     int tpb;   // pixel tiles per block (pipelined kernel): consecutive tiles of one sample
     int vert;  // 1: the block walks its tpb tiles down H (W-neighbours run concurrently), 0: along W
     int xcd;   // 1: blockIdx.x is remapped so that each XCD owns a contiguous range of tiles
-    // optional GroupNorm statistics of the OUTPUT for the next GroupNorm (lc_groupnorm_apply_os):
-    // per sample, channel octet (8 consecutive channels) and wave tile one entry
-    // (pivot, n, sum(y - pivot), sum((y - pivot)^2));  ostats[(b*Co/8 + octet)*oslots + slot],
-    // slot = (tile_row*tiles_w + tile_col)*WPX + wave_px.  Pipelined kernel only.
-    // ounit = 2: one entry per channel PAIR instead (ostats[(b*Co/2 + pair)*oslots + slot]) -- for a consumer
-    // GroupNorm with 2 / 4 / 6 channels per group (GroupNorm32 at 64 ... 192 channels); deferred epilogue only.
+    // optional GroupNorm statistics entries of the OUTPUT for the next GroupNorm (stats_entry.h): one per sample,
+    // channel unit and wave tile.  ounit = 8: octets; 2: channel PAIRS -- for a consumer GroupNorm with 2 / 4 / 6 channels
+    // per group (GroupNorm32 at 64 ... 192 channels), deferred epilogue only; 4: quads, pre-split and stride-2 kernels.
     f32x4* ostats;
     int oslots, ounit;
 };
@@ -146,9 +144,9 @@ __device__ __forceinline__ f32x4 gn_row_from_stats(const lc_gn_stats_input& gs, 
     return r;
 }
 
-// The same rows from the PRODUCER's octet statistics (the fold of gn_apply_os_kernel, norm.hip):
-// wave w folds the entries of groups w, w + nwaves, ... in fp64 around the group's first pivot,
-// then every thread builds the rows of its channels.  All NT threads of the block call this.
+// The same rows from the PRODUCER's statistics entries (stats_entry.h): wave w folds the entries of
+// groups w, w + nwaves, ..., then every thread builds the rows of its channels.  All NT threads of the
+// block call this.
 constexpr int GN_MAX_G = 128;
 template <int NT>
 __device__ __forceinline__ void gn_rows_from_ostats(const ConvArgsH& a, int b, int tid, f32x4* ctab,
@@ -164,37 +162,13 @@ __device__ __forceinline__ void gn_rows_from_ostats(const ConvArgsH& a, int b, i
         if (a.gs.shift) sh0 = a.gs.shift[b * a.gs.ss_bs + tid];
     }
     for (int g = tid >> 6; g < G; g += NT / 64) {
-        const int cg0 = g * cpg;
-        const bool s1 = cg0 >= a.seg[0].channels;
-        const int slots = s1 ? a.seg[1].slots : a.seg[0].slots;
-        const int ush = s1 ? a.seg[1].ush : a.seg[0].ush;
-        const f32x4* e =
-            s1 ? a.seg[1].p + ((long long)b * (a.seg[1].channels >> ush) + ((cg0 - a.seg[0].channels) >> ush)) * slots
-               : a.seg[0].p + ((long long)b * (a.seg[0].channels >> ush) + (cg0 >> ush)) * slots;
-        const int n_ent = (cpg >> ush) * slots;
-        const double P0 = (double)e[0].x;
+        const StatGroup sg = stat_group(a.segs, b, g * cpg, cpg);
+        const double P0 = (double)sg.e[0].x;
         double N = 0.0, S = 0.0, Q = 0.0;
-        for (int base = lane; base < n_ent; base += 64 * 16) {   // 16 loads in flight per lane
-            f32x4 v[16];
-#pragma unroll
-            for (int k = 0; k < 16; ++k)
-                v[k] = base + 64 * k < n_ent ? e[base + 64 * k] : f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int k = 0; k < 16; ++k) {                      // an absent entry (n = 0) adds nothing
-                const double n = v[k].y, d = (double)v[k].x - P0, s_ = v[k].z;
-                N += n;
-                S += s_ + n * d;
-                Q += (double)v[k].w + d * (2.0 * s_ + n * d);
-            }
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            N += __shfl_xor(N, o, 64); S += __shfl_xor(S, o, 64); Q += __shfl_xor(Q, o, 64);
-        }
-        const double m = N > 0.0 ? S / N : 0.0;
-        double var = N > 0.0 ? Q / N - m * m : 0.0;
-        if (var < 0.0) var = 0.0;
-        if (lane == 0) gtab[g] = float2{(float)(P0 + m), (float)(1.0 / sqrt(var + (double)a.gs.eps))};
+        fold_entries<64, 16>(sg.e, sg.n_ent, lane, P0, N, S, Q);   // 16 loads in flight per lane
+        stat_wave_sum(N, S, Q);
+        const float2 ms = stat_finish(N, S, Q, P0, a.gs.eps);
+        if (lane == 0) gtab[g] = ms;
     }
     __syncthreads();
     for (int c = tid; c < a.Cgn; c += NT) {
@@ -311,48 +285,6 @@ __device__ __forceinline__ void split_store(const float (&v)[8], float xs, half8
     *dst_lo = lo;
 }
 
-// 64-lane sum with DPP adds (VALU rate, no LDS): row_shr 1,2,4,8, then row_bcast:15 into rows 1,3
-// and row_bcast:31 into rows 2,3 -- lane 63 ends up with the total.
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ float dpp_add(float v) {
-    return v + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v),
-                                                                     CTRL, ROW_MASK, 0xF, true));
-}
-__device__ __forceinline__ float wave_sum_to_lane63(float v) {
-    v = dpp_add<0x111, 0xF>(v);
-    v = dpp_add<0x112, 0xF>(v);
-    v = dpp_add<0x114, 0xF>(v);
-    v = dpp_add<0x118, 0xF>(v);
-    v = dpp_add<0x142, 0xA>(v);
-    v = dpp_add<0x143, 0xC>(v);
-    return v;
-}
-
-// the same without the last step: lanes 31 / 63 hold the sums of lanes 0-31 / 32-63
-__device__ __forceinline__ float half_sum_to_lane31_63(float v) {
-    v = dpp_add<0x111, 0xF>(v);
-    v = dpp_add<0x112, 0xF>(v);
-    v = dpp_add<0x114, 0xF>(v);
-    v = dpp_add<0x118, 0xF>(v);
-    v = dpp_add<0x142, 0xA>(v);
-    return v;
-}
-
-// One statistics entry (pivot, n, s, q) as ONE 32-bit buffer store: the sums sit in the reducing lane R (63, or 31 and 63
-// for two half-wave entries), pivot and count are wave-uniform; lanes R-3 .. R carry the fields 0 .. 3 (their voffset =
-// entry byte offset + 4 * (lane & 3); every other lane: an out-of-range offset).  No wide store data, no waits (DefEpi's
-// store_entry_lanes, for epilogues outside that struct).
-__device__ __forceinline__ void store_entry_4lanes(__amdgpu_buffer_rsrc_t rs, float p_, float n_, float s_, float q_,
-                                                   unsigned voffset) {
-    const float s1 = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, s_), 0x101, 0xF, 0xF, true));
-    const int f = (int)(threadIdx.x & 3);
-    const unsigned k0 = (unsigned)((f - 1) >> 31), k1 = (unsigned)(((f ^ 1) - 1) >> 31);
-    const unsigned k2 = (unsigned)(((f ^ 2) - 1) >> 31), k3 = (unsigned)(((f ^ 3) - 1) >> 31);
-    const unsigned vu = (__float_as_uint(p_) & k0) | (__float_as_uint(n_) & k1) | (__float_as_uint(s1) & k2) |
-                        (__float_as_uint(q_) & k3);
-    __builtin_amdgcn_raw_buffer_store_b32(vu, rs, voffset, 0, 0);
-}
-
 // one LDS-DMA wave-instruction: 64 lanes x 16 bytes, global (descriptor + per-lane voffset + uniform
 // soffset; out of range -> zeros) -> LDS at dst + 16 * lane.  (The builtin exists in the device
 // pass only; the host pass needs just the kernel's stub.)
@@ -419,14 +351,14 @@ struct DefEpi {                // branch here split the MFMAs' basic block -- le
 
     f32x16 accp[TCO][TPX];
     float rq[RING];
-    float st_p, st_s, st_q;    // the running octet: pivot, sum (v - p), sum (v - p)^2 of channels q = 0, 1 of each quad
-    float st_s2, st_q2;        // pair entries: ... and of channels q = 2, 3 (unused for octet entries)
-    // Pair entries: every entry has a pivot of ITS OWN channels -- st_p is then per lane (lanes 0-31: lane 0's first
-    // value of q = 0, lanes 32-63: lane 32's), st_p2 the same for q = 2, 3.  With the octet's one pivot a pair whose level
-    // sits D away from the octet's first channel summed d ~ D in float32 and lost (D / std)^2 ulps of its variance
-    // (GroupNorm32 on channels at different levels: tests/test_gn_structured.py).
-    float st_p2;
     static constexpr bool pairs = EMIT == 2;   // entries per channel pair (ConvArgsH::ounit == 2)
+    // The running octet as plain fields, not two StatAcc (stats_entry.h): with the accumulator type every pair-entry
+    // instantiation came out with one more vmcnt(0) wait or exec-mask branch (profiles/stats_entry.txt).  The pivots come
+    // from the shared stat_pivot.
+    static constexpr StatPivot PV = pairs ? PIVOT_HALF : PIVOT_WAVE;
+    float st_p, st_s, st_q;    // pivot, sum (v - p), sum (v - p)^2 of channels q = 0, 1 of each quad (octets: of all)
+    float st_s2, st_q2;        // pair entries: ... and of channels q = 2, 3 (unused for octet entries)
+    float st_p2;               // ... around a pivot of ITS OWN channels (the pivot rule)
     unsigned voff[TPX];        // byte offset of (channel co_wave, pixel j) in the sample; OOB = nothing to do
     __amdgpu_buffer_rsrc_t rs_y, rs_r, rs_o;
     float out_unscale, out_scale;
@@ -476,13 +408,6 @@ struct DefEpi {                // branch here split the MFMAs' basic block -- le
         rq[k % RING] = __builtin_bit_cast(
             float, __builtin_amdgcn_raw_buffer_load_b32(rs_r, off_of(k), (unsigned)cor_of(k) * HW4, 0));
     }
-    // the pivot of an entry: lane 0's value for the whole wave (octet entries), or lane 0's for lanes 0-31 and lane 32's
-    // for lanes 32-63 (pair entries: one entry per half-wave)
-    static __device__ __forceinline__ float half_pivot(float v) {
-        const float lo = lc_readlane_f32(v, 0);
-        if constexpr (!pairs) return lo;
-        else return lc_half_select(lo, lc_readlane_f32(v, 32));
-    }
     __device__ __forceinline__ void finalize(int k) { finalize_with(k, rq[k % RING]); }
     __device__ __forceinline__ void finalize_with(int k, float res) {
         const int i = i_of(k), m = m_of(k), j = j_of(k), r = 4 * m + (k & 3);
@@ -496,55 +421,28 @@ struct DefEpi {                // branch here split the MFMAs' basic block -- le
         if constexpr (EMIT) {
             const bool pok = voff[j] != OOB;
             if (k % OCTV == 0) {
-                st_p = half_pivot(pok ? v : 0.0f);
+                st_p = stat_pivot<PV>(pok ? v : 0.0f);
                 st_s = 0.f; st_q = 0.f; st_s2 = 0.f; st_q2 = 0.f;
             }
-            if (pairs && k % OCTV == 2) st_p2 = half_pivot(pok ? v : 0.0f);      // first value of channels q = 2, 3
+            if (pairs && k % OCTV == 2) st_p2 = stat_pivot<PV>(pok ? v : 0.0f);      // first value of channels q = 2, 3
             const float d = pok ? v - ((pairs && (k & 2)) ? st_p2 : st_p) : 0.0f;    // (k & 3 = channel inside the lane's quad)
             if (pairs && (k & 2)) { st_s2 += d; st_q2 = fmaf(d, d, st_q2); }
             else { st_s += d; st_q = fmaf(d, d, st_q); }
             if (k % OCTV == OCTV - 1) {                  // the octet is complete
                 const int oct = i * 4 + m;               // octet index inside this wave's channel rows
                 const bool ok = ent_off != OOB && co_wave + i * 32 + 8 * m < Co;   // (co_wave carries 4 * kh <= 4)
-                // The entry goes out as ONE 32-bit store in which the four lanes below the reducing lane carry one
-                // field each (store_entry_lanes).  Rounds 1-3 wrote it as one 128-bit buffer store with an SGPR
-                // soffset; ~3 entries in 10^7 then arrived with a foreign upper dword (a VALU write of the data
-                // registers one or two instructions behind the store: LLVM exempts MUBUF stores with an SGPR soffset
-                // from the ISA's ">64-bit store data" wait state, and under ~27 stores in flight per wave that
-                // exemption does not hold on gfx950).  Measured in round 4 (devtools/entry_stress.py,
-                // profiles/r04_entry_store.txt): 128-bit + SGPR soffset 17 bad entries in 5e7, 32-bit stores 0 in
-                // 1e8.  32-bit stores fetch their data at issue -- the form every output value of this epilogue
-                // has always used.
-                const unsigned vo = ok ? ent_off : OOB;
+                const unsigned vo = ok ? ent_off : OOB;  // (ent_off of lanes R-3 .. R = entry + 4 * field, OOB elsewhere)
                 if constexpr (!pairs) {                  // one entry from lane 63
-                    store_entry_lanes(st_p, nv8, wave_sum_to_lane63(st_s), wave_sum_to_lane63(st_q), vo,
-                                  (unsigned)oct * oct_stride);
+                    store_entry_4lanes(rs_o, st_p, nv8, wave_sum_to_lane63(st_s), wave_sum_to_lane63(st_q), vo,
+                                       (unsigned)oct * oct_stride);
                 } else {                                 // pairs (8m + 4kh + 0,1) and (+ 2,3) from lanes 31 / 63
-                    store_entry_lanes(st_p, nv8, half_sum_to_lane31_63(st_s), half_sum_to_lane31_63(st_q), vo,
-                                  (unsigned)(4 * oct) * oct_stride);
-                    store_entry_lanes(st_p2, nv8, half_sum_to_lane31_63(st_s2), half_sum_to_lane31_63(st_q2), vo,
-                                  (unsigned)(4 * oct + 1) * oct_stride);
+                    store_entry_4lanes(rs_o, st_p, nv8, half_sum_to_lane31_63(st_s), half_sum_to_lane31_63(st_q), vo,
+                                       (unsigned)(4 * oct) * oct_stride);
+                    store_entry_4lanes(rs_o, st_p2, nv8, half_sum_to_lane31_63(st_s2), half_sum_to_lane31_63(st_q2), vo,
+                                       (unsigned)(4 * oct + 1) * oct_stride);
                 }
             }
         }
-    }
-    // (pivot, n, s, q): the sums arrive in the reducing lane R (63, or 31 / 63 for pair entries), pivot and count are
-    // wave-uniform; lanes R-3 .. R store the fields 0 .. 3 (ent_off of those lanes = entry + 4 * field, OOB elsewhere):
-    // one store instruction per entry, no wide store data.  (First form of round 4: four 32-bit stores from lane R with
-    // four different cache-policy bits to keep the load/store optimizer from re-merging them -- the sc0 sc1 one cost
-    // the level-0 launch ~100 us.)
-    __device__ __forceinline__ void store_entry_lanes(float p_, float n_, float s_, float q_, unsigned voffset,
-                                                      unsigned soffset) {
-        // row_shl:1 -- lane R-1 reads lane R's sum
-        const float s1 = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, s_), 0x101, 0xF, 0xF, true));
-        // field select by lane & 3 with masks, not selects: hipcc turned the nested ?: (one arm is a DPP result) into
-        // exec-mask BRANCHES -- four basic-block splits per tile inside the MFMA stream (ISA of rounds 3-4)
-        const int f = (int)(threadIdx.x & 3);
-        const unsigned k0 = (unsigned)((f - 1) >> 31), k1 = (unsigned)(((f ^ 1) - 1) >> 31);
-        const unsigned k2 = (unsigned)(((f ^ 2) - 1) >> 31), k3 = (unsigned)(((f ^ 3) - 1) >> 31);
-        const unsigned vu = (__float_as_uint(p_) & k0) | (__float_as_uint(n_) & k1) | (__float_as_uint(s1) & k2) |
-                            (__float_as_uint(q_) & k3);
-        __builtin_amdgcn_raw_buffer_store_b32(vu, rs_o, voffset, soffset, 0);
     }
     // slot s of the deferred stream (s static after unrolling)
     __device__ __forceinline__ void slot(int s) {

@@ -177,7 +177,7 @@ __global__ __launch_bounds__(512, 1) void conv_f16x2_pp_kernel(ConvArgsH a) {
     if constexpr (GNM != 0) {
         if (a.gs.partials) {
             for (int i = tid; i < a.Cgn; i += G::NT) ctab[i] = gn_row_from_stats(a.gs, xptr, b, i, a.Ci, HW);
-        } else if (a.seg[0].p) {
+        } else if (a.segs.seg[0].p) {
             gn_rows_from_ostats<G::NT>(a, b, tid, ctab, gtab);
         } else {
             const f32x4* g = a.gn + (long long)b * a.Cgn;
@@ -309,39 +309,34 @@ __global__ __launch_bounds__(512, 1) void conv_f16x2_pp_kernel(ConvArgsH a) {
         // into one body with a run-time index into the parked set -- which then lives in scratch memory, and every
         // scratch access in a stage slot is a vmcnt(0) that drains the loads just issued)
         asm volatile("; epilogue octet %0" ::"n"(m));
-        float st_p = 0.f, st_s = 0.f, st_q = 0.f, st_s2 = 0.f, st_q2 = 0.f;
-        float st_p2 = 0.f;      // pair entries: st_p / st_p2 are per lane, a pivot of each entry's own channels (DefEpi)
-        auto half_pivot = [&](float v) __attribute__((always_inline)) {
-            const float lo = lc_readlane_f32(v, 0);
-            if constexpr (!pairs) return lo;
-            else return lc_half_select(lo, lc_readlane_f32(v, 32));
-        };
+        // st[0] alone (octet entries), or channels q = 0, 1 and q = 2, 3 of each lane's quad (pair entries: each entry
+        // around a pivot of its own channels)
+        StatAcc<pairs ? PIVOT_HALF : PIVOT_WAVE> st[2] = {{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}};
 #pragma unroll
         for (int k = 0; k < 4 * TPX; ++k) {
             const int j = k >> 2, q = k & 3;
             const float v = fmaf(accp[j][4 * m + q], out_unscale, res[k]) * out_scale;
             ov[k] = v;
             if constexpr (EMIT != 0) {
-                if (k == 0) st_p = half_pivot(v);
-                if (pairs && k == 2) st_p2 = half_pivot(v);
-                const float d = v - ((pairs && (q & 2)) ? st_p2 : st_p);
-                if (pairs && (q & 2)) { st_s2 += d; st_q2 = fmaf(d, d, st_q2); }
-                else { st_s += d; st_q = fmaf(d, d, st_q); }
+                if (k == 0) st[0].start(v);
+                if (pairs && k == 2) st[1].start(v);
+                st[(pairs && (q & 2)) ? 1 : 0].add(v);
             }
         }
         ev[0] = ev[1] = 0.f;
         if constexpr (EMIT != 0) {
-            // one 32-bit store per entry: lanes R-3 .. R carry the four fields (see DefEpi::store_entry_lanes)
+            // one 32-bit store per entry: lanes R-3 .. R carry the four fields (see store_entry_4lanes)
             auto entry = [&](float p_, float n_, float s_, float q_) __attribute__((always_inline)) {
                 const float s1 = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, s_), 0x101, 0xF, 0xF, true));
                 const unsigned f = lane & 3;
                 return f == 0 ? p_ : (f == 1 ? n_ : (f == 2 ? s1 : q_));
             };
             if constexpr (!pairs) {
-                ev[0] = entry(st_p, 8.0f * 32.0f * TPX, wave_sum_to_lane63(st_s), wave_sum_to_lane63(st_q));
+                ev[0] = entry(st[0].p, 8.0f * 32.0f * TPX, wave_sum_to_lane63(st[0].s), wave_sum_to_lane63(st[0].q));
             } else {
-                ev[0] = entry(st_p, 2.0f * 32.0f * TPX, half_sum_to_lane31_63(st_s), half_sum_to_lane31_63(st_q));
-                ev[1] = entry(st_p2, 2.0f * 32.0f * TPX, half_sum_to_lane31_63(st_s2), half_sum_to_lane31_63(st_q2));
+#pragma unroll
+                for (int e = 0; e < 2; ++e)
+                    ev[e] = entry(st[e].p, 2.0f * 32.0f * TPX, half_sum_to_lane31_63(st[e].s), half_sum_to_lane31_63(st[e].q));
             }
         }
     };

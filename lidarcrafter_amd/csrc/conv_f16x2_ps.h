@@ -324,9 +324,9 @@ __global__ __launch_bounds__(C::NT, C::NT / 256) void conv_f16x2_ps_kernel(ConvA
             continue;
         }
         // ---- epilogue: as conv_f16x2_pipe_kernel --------------------------------------------
-        // (st_ph: quad entries -- the upper half-wave's quad 8m+4 .. 8m+7 has a pivot of its own channels; not used for octets)
-        float st_p[C::TCO_][4], st_ph[C::TCO_][4], st_s[C::TCO_][4], st_q[C::TCO_][4];
-        const bool upper_quad = a.ounit == 4 && (lane & 32);
+        // (quad entries: the upper half-wave's quad 8m+4 .. 8m+7 has a pivot of its own channels)
+        StatAcc<PIVOT_HALF_RT> st[C::TCO_][4];
+        const bool quads = a.ounit == 4, upper_quad = quads && (lane & 32);
         int nvalid = 0;
 #pragma unroll
         for (int j = 0; j < C::TPX_; ++j) {
@@ -352,47 +352,27 @@ __global__ __launch_bounds__(C::NT, C::NT / 256) void conv_f16x2_ps_kernel(ConvA
                                                               (unsigned)(i * 32 + (r & 3) + 8 * (r >> 2)) * HW4, LC_DEF_AUX);
                     if constexpr (EMIT_STATS && !(LC_EMIT_ABL & 1)) {
                         const int m = r >> 2;
-                        if (j == 0 && (r & 3) == 0) {
-                            st_p[i][m] = lc_readlane_f32(pok ? v : 0.0f, 0);
-                            st_ph[i][m] = lc_readlane_f32(pok ? v : 0.0f, 32);
-                            st_s[i][m] = 0.f; st_q[i][m] = 0.f;
-                        }
-                        const float d = pok ? v - (upper_quad ? st_ph[i][m] : st_p[i][m]) : 0.0f;
-                        st_s[i][m] += d;
-                        st_q[i][m] = fmaf(d, d, st_q[i][m]);
+                        if (j == 0 && (r & 3) == 0) st[i][m].start(pok ? v : 0.0f, upper_quad);
+                        st[i][m].add(v, pok);
                     }
                     acc[i][j][r] = 0.0f;
                 }
             }
         }
         if constexpr (EMIT_STATS && !(LC_EMIT_ABL & 2)) {
-            // One 32-bit buffer store per entry, fields spread over the four lanes below the reducing lane (round 5: the
-            // first form -- four volatile 32-bit stores from that lane -- compiled to sc0 sc1 stores with a vmcnt(0) behind
-            // each, i.e. every entry waited for all of the tile's output stores: +6 ... +11 us per launch,
-            // profiles/r05_level0.txt section 7).  Octet entries: lane 63 holds the sums; quad entries (a consumer
-            // GroupNorm with 4 / 12 channels per group): lanes 0-31 hold channels 8m .. 8m+3, lanes 32-63 8m+4 .. 8m+7
-            // -- the two half-wave sums in lanes 31 / 63, each around a pivot of its own quad (lanes 0 / 32).
+            // octet entries, or quad entries on request (emit_octet_or_quads, stats_entry.h)
             const int slot = ((h0 / C::TH_) * a.tiles_w + w0 / C::TW_) * C::WPX_ + wpx;
             const int co_blk = co0 + wco * C::TCO_ * 32;
-            const bool quads = a.ounit == 4;
             const int ush = quads ? 2 : 3;
             const unsigned ebytes = (unsigned)(a.Co >> ush) * (unsigned)a.oslots * 16u;
             const __amdgpu_buffer_rsrc_t rs_o = __builtin_amdgcn_make_buffer_rsrc(
                 (void*)(a.ostats + (long long)b * (a.Co >> ush) * a.oslots), 0, ebytes, 0x00020000);
-            const bool mine = quads ? (lane & 31) >= 28 : lane >= 60;
-            const float nv = (float)((quads ? 4 : 8) * nvalid);
 #pragma unroll
             for (int i = 0; i < C::TCO_; ++i) {
 #pragma unroll
                 for (int m = 0; m < 4; ++m) {
                     const int co_oct = co_blk + i * 32 + 8 * m;
-                    const float sh = half_sum_to_lane31_63(st_s[i][m]), qh = half_sum_to_lane31_63(st_q[i][m]);
-                    const float sf = dpp_add<0x143, 0xC>(sh), qf = dpp_add<0x143, 0xC>(qh);   // lane 63: the wave's sum
-                    const int ent = quads ? (co_oct >> 2) + (lane >> 5) : (co_oct >> 3);
-                    const unsigned vo = (mine && co_oct < a.Co)
-                                            ? ((unsigned)ent * (unsigned)a.oslots + (unsigned)slot) * 16u + 4u * (lane & 3)
-                                            : 0x80000000u;
-                    store_entry_4lanes(rs_o, upper_quad ? st_ph[i][m] : st_p[i][m], nv, quads ? sh : sf, quads ? qh : qf, vo);
+                    emit_octet_or_quads(rs_o, st[i][m], quads, nvalid, co_oct, co_oct < a.Co, a.oslots, slot);
                 }
             }
         }

@@ -331,7 +331,7 @@ __global__ __launch_bounds__(256, 1) void conv_s2_shared_w_kernel(ConvArgsH a) {
         const bool pok = gh < H && gw < W;
         const unsigned vo = pok ? (unsigned)(co_wave * HW + gh * W + gw) * 4u : OOB;
         const float brow = (gh == 0 ? 0.875f : 1.0f) + (gh == H - 1 ? 0.875f : 1.0f) - 1.0f;
-        float st_p[4], st_ph[4], st_s[4], st_q[4];      // (st_ph: the upper half-wave's quad has a pivot of its own channels)
+        StatAcc<PIVOT_HALF_RT> st[4];                   // (quads: the upper half-wave's quad has a pivot of its own channels)
         const bool upper_quad = quads && (lane & 32);
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
@@ -341,30 +341,17 @@ __global__ __launch_bounds__(256, 1) void conv_s2_shared_w_kernel(ConvArgsH a) {
                                                   (unsigned)cor * HW4, LC_DEF_AUX);
             if constexpr (EMIT_STATS) {
                 const int m = r >> 2;
-                if ((r & 3) == 0) {
-                    st_p[m] = lc_readlane_f32(pok ? v : 0.0f, 0); st_ph[m] = lc_readlane_f32(pok ? v : 0.0f, 32);
-                    st_s[m] = 0.f; st_q[m] = 0.f;
-                }
-                const float d = pok ? v - (upper_quad ? st_ph[m] : st_p[m]) : 0.0f;
-                st_s[m] += d;
-                st_q[m] = fmaf(d, d, st_q[m]);
+                if ((r & 3) == 0) st[m].start(pok ? v : 0.0f, upper_quad);
+                st[m].add(v, pok);
             }
         }
         if constexpr (EMIT_STATS) {
             const int nvalid = __popcll(__ballot(pok) & 0xFFFFFFFFull);
             const int slot = (gh * a.tiles_w + tw_i) * 2 + wpx;
-            const bool mine = quads ? (lane & 31) >= 28 : lane >= 60;
-            const float nv = (float)((quads ? 4 : 8) * nvalid);
 #pragma unroll
             for (int m = 0; m < 4; ++m) {
                 const int co_oct = co0 + wco * 32 + 8 * m;
-                const float sh = half_sum_to_lane31_63(st_s[m]), qh = half_sum_to_lane31_63(st_q[m]);
-                const float sf = dpp_add<0x143, 0xC>(sh), qf = dpp_add<0x143, 0xC>(qh);
-                const int ent = quads ? (co_oct >> 2) + (lane >> 5) : (co_oct >> 3);
-                const unsigned eo = (mine && co_oct < a.Co && gh < H)
-                                        ? ((unsigned)ent * (unsigned)a.oslots + (unsigned)slot) * 16u + 4u * (lane & 3)
-                                        : OOB;
-                store_entry_4lanes(rs_o, upper_quad ? st_ph[m] : st_p[m], nv, quads ? sh : sf, quads ? qh : qf, eo);
+                emit_octet_or_quads(rs_o, st[m], quads, nvalid, co_oct, co_oct < a.Co && gh < H, a.oslots, slot);
             }
         }
     }
@@ -425,7 +412,7 @@ extern "C" int lc_conv2d_ring_s2_f16x2_ps_fwd(const void* x_split, const void* w
     a.out_scale = out_scale;
     a.gn = nullptr; a.Cgn = 0; a.gn_silu = 0;
     a.gs = lc_gn_stats_input{nullptr, 0, 0, 0.f, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr};
-    a.seg[0] = a.seg[1] = ConvArgsH::OctSeg{nullptr, 0, 0, 3};
+    a.segs = STAT_SEGS_NONE;
     a.ostats = nullptr; a.oslots = 0; a.ounit = 8;
     if (gn_ostats_out) {
         if (Co % 8 || (gn_ostats_unit != 8 && gn_ostats_unit != 4)) return LC_EUNSUP;

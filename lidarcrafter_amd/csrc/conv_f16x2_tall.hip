@@ -306,7 +306,7 @@ __global__ __launch_bounds__(512, 2) void conv_f16x2_tall_kernel(ConvArgsH a) {
     if constexpr (GNM != 0) {   // rows of the fused input norm (as conv_f16x2_pipe_kernel), repacked per channel pair
         if (a.gs.partials) {
             for (int i = tid; i < a.Cgn; i += G::NT) ctab[i] = gn_row_from_stats(a.gs, xptr, b, i, a.Ci, HW);
-        } else if (a.seg[0].p) {
+        } else if (a.segs.seg[0].p) {
             gn_rows_from_ostats<G::NT>(a, b, tid, ctab, gtab);
         } else {
             const f32x4* g = a.gn + (long long)b * a.Cgn;

@@ -4,6 +4,7 @@
 // tensor once (float4, fp32 lane partials over <=64 values, fp64 wave/block reduction),
 // apply reads once and writes once.  A group is a contiguous span of (C/G)*H*W floats in NCHW.
 #include "common.h"
+#include "stats_entry.h"
 
 namespace {
 
@@ -149,85 +150,23 @@ __global__ void gn_coeffs_kernel(const double* __restrict__ part, const float* _
 
 
 // ---------------------------------------------------------------------------------------------
-// GroupNorm apply fed by the PRODUCER's statistics (conv epilogue, conv_f16x2.hip): entries
-// (pivot, n, S = sum(y - pivot), Q = sum((y - pivot)^2)) per (sample, octet of 8 channels, wave
-// tile); a group's entries are contiguous.  Every entry is re-centred on ONE common pivot P0 (the
-// group's first entry's pivot, a typical value of the tensor):
-//   S' = S + n d,  Q' = Q + d (2 S + n d),  d = pivot - P0
-// and fp64 sums of N, S', Q' give mean = P0 + S'/N, var = Q'/N - (S'/N)^2: no division per entry,
-// no cancellation beyond |mean - P0| / std (a few), fixed summation order (deterministic).
-struct OctStats2 {
-    const f32x4* p0; const f32x4* p1;     // segment 0: channels [0, c0), segment 1: [c0, c0 + c1)
-    int c0, slots0, c1, slots1;
-    int ush0, ush1;                       // log2(channels per entry) of each segment: 3 octets, 2 quads, 1 pairs, 0 channels
-};
-// lc_oct_stats -> one OctStats2 segment; false: not a unit this library writes
-static bool os_unit_shift(int unit, int& ush) {
-    switch (unit) { case 8: ush = 3; return true; case 4: ush = 2; return true; case 2: ush = 1; return true;
-                    case 1: ush = 0; return true; default: return false; }
-}
-// The segments of a statistics-fed GroupNorm: every group must be whole entries of ONE segment.
-static int os_from_segments(const lc_oct_stats* s0, const lc_oct_stats* s1, int C, int cpg, OctStats2& os) {
-    if (!s0 || !s0->p || s0->channels <= 0 || s0->slots <= 0) return LC_EINVAL;
-    if (s1 && (!s1->p || s1->channels <= 0 || s1->slots <= 0)) return LC_EINVAL;
-    os.p0 = reinterpret_cast<const f32x4*>(s0->p); os.c0 = s0->channels; os.slots0 = s0->slots;
-    os.p1 = nullptr; os.c1 = 0; os.slots1 = 0; os.ush0 = os.ush1 = 3;
-    if (!os_unit_shift(s0->unit, os.ush0)) return LC_EUNSUP;
-    if (s1) {
-        os.p1 = reinterpret_cast<const f32x4*>(s1->p); os.c1 = s1->channels; os.slots1 = s1->slots;
-        if (!os_unit_shift(s1->unit, os.ush1)) return LC_EUNSUP;
-    }
-    if (os.c0 + os.c1 != C || os.c0 % cpg || cpg % s0->unit || os.c0 % s0->unit ||
-        (s1 && (cpg % s1->unit || os.c1 % s1->unit)))
-        return LC_EUNSUP;
-    return LC_OK;
-}
-
+// GroupNorm apply fed by the PRODUCER's statistics entries (stats_entry.h: format, re-centring fold, segments): one block
+// folds its group's entries, then streams its slab.
 __global__ __launch_bounds__(256) void gn_apply_os_kernel(
-    const float* __restrict__ x, long long x_bs, OctStats2 os, const float* __restrict__ gamma,
+    const float* __restrict__ x, long long x_bs, StatSegs os, const float* __restrict__ gamma,
     const float* __restrict__ beta, const float* __restrict__ scale, const float* __restrict__ shift,
     long long ss_bs, float* __restrict__ y, long long y_bs, int C, int G, long long HW, float eps,
     int act, int cpb) {
     __shared__ double sh[12];
     const int c_first = blockIdx.y * cpb, b = blockIdx.z;
     const int cpg = C / G, g = c_first / cpg;
-    const int cg0 = g * cpg;                                   // first channel of the group
-    const bool seg1 = cg0 >= os.c0;
-    const int slots = seg1 ? os.slots1 : os.slots0;
-    const int ush = seg1 ? os.ush1 : os.ush0;
-    const f32x4* e = seg1 ? os.p1 + ((long long)b * (os.c1 >> ush) + ((cg0 - os.c0) >> ush)) * slots
-                          : os.p0 + ((long long)b * (os.c0 >> ush) + (cg0 >> ush)) * slots;
-    const int n_ent = (cpg >> ush) * slots;
-    const double P0 = (double)e[0].x;
+    const StatGroup sg = stat_group(os, b, g * cpg, cpg);
+    const double P0 = (double)sg.e[0].x;
     double N = 0.0, S = 0.0, Q = 0.0;
-    for (int base = threadIdx.x; base < n_ent; base += 256 * 4) {   // 4 loads in flight per thread
-        f32x4 v[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            v[k] = base + 256 * k < n_ent ? e[base + 256 * k] : f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {                               // an absent entry (n = 0) adds nothing
-            const double n = v[k].y, d = (double)v[k].x - P0, s_ = v[k].z;
-            N += n;
-            S += s_ + n * d;
-            Q += (double)v[k].w + d * (2.0 * s_ + n * d);
-        }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        N += __shfl_xor(N, o, 64); S += __shfl_xor(S, o, 64); Q += __shfl_xor(Q, o, 64);
-    }
-    const int wv = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { sh[3 * wv] = N; sh[3 * wv + 1] = S; sh[3 * wv + 2] = Q; }
-    __syncthreads();
-    N = (sh[0] + sh[3]) + (sh[6] + sh[9]);
-    S = (sh[1] + sh[4]) + (sh[7] + sh[10]);
-    Q = (sh[2] + sh[5]) + (sh[8] + sh[11]);
-    const double m = N > 0.0 ? S / N : 0.0;
-    double var = N > 0.0 ? Q / N - m * m : 0.0;
-    if (var < 0.0) var = 0.0;
-    const float mu = (float)(P0 + m);
-    const float rstd = (float)(1.0 / sqrt(var + (double)eps));
+    fold_entries<256, 4>(sg.e, sg.n_ent, threadIdx.x, P0, N, S, Q);   // 4 loads in flight per thread
+    stat_block_sum(sh, N, S, Q);
+    const float2 ms = stat_finish(N, S, Q, P0, eps);
+    const float mu = ms.x, rstd = ms.y;
     const long long per = (HW + gridDim.x - 1) / gridDim.x;
     const long long lo = blockIdx.x * per;
     const long long hi = lo + per < HW ? lo + per : HW;
@@ -419,7 +358,7 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(
 // +9 us per pass at 8 x 128 x 16 x 512 and 3-5 % on the C2 step (profiles/r05_level0.txt section 8).
 template <int OS>
 __global__ __launch_bounds__(256) void gn_apply_split_kernel(
-    const float* __restrict__ x, long long x_bs, const double* __restrict__ part, OctStats2 os,
+    const float* __restrict__ x, long long x_bs, const double* __restrict__ part, StatSegs os,
     const float* __restrict__ gamma, const float* __restrict__ beta, const float* __restrict__ scale,
     const float* __restrict__ shift, long long ss_bs, half8_t* __restrict__ ysp, long long ysp_bs,
     int C, int G, long long HW, int nch, float eps, int act, lc_conv_range* range) {
@@ -484,97 +423,38 @@ __global__ __launch_bounds__(256) void gn_apply_split_kernel(
         const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
         const int ng = 8 / cpg;                                    // 4 or 2 groups in this octet
         const int cg0 = (g + (wv < ng ? wv : ng - 1)) * cpg;       // (waves past the last group redo it: no divergence)
-        const bool seg1 = cg0 >= os.c0;
-        const int slots = seg1 ? os.slots1 : os.slots0;
-        const int ush = seg1 ? os.ush1 : os.ush0;
-        const f32x4* e = seg1 ? os.p1 + ((long long)b * (os.c1 >> ush) + ((cg0 - os.c0) >> ush)) * slots
-                              : os.p0 + ((long long)b * (os.c0 >> ush) + (cg0 >> ush)) * slots;
-        const int n_ent = (cpg >> ush) * slots;
-        const float P0f = e[0].x;
+        const StatGroup sg = stat_group(os, b, cg0, cpg);
+        const float P0f = sg.e[0].x;
         double N = 0.0, S = 0.0, Q = 0.0;
         f32x4 v[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) v[k] = lane + 64 * k < n_ent ? e[lane + 64 * k] : f32x4{0.f, 0.f, 0.f, 0.f};
+        load_entries<64, 4>(v, sg.e, sg.n_ent, lane);
         issue_first();
         const double P0 = (double)P0f;
-        auto fold4 = [&](const f32x4 (&w)[4]) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const double n = w[k].y, d = (double)w[k].x - P0, s_ = w[k].z;
-                N += n;
-                S += s_ + n * d;
-                Q += (double)w[k].w + d * (2.0 * s_ + n * d);
-            }
-        };
-        fold4(v);
-        for (int base = lane + 64 * 4; base < n_ent; base += 64 * 4) {
-            f32x4 w[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) w[k] = base + 64 * k < n_ent ? e[base + 64 * k] : f32x4{0.f, 0.f, 0.f, 0.f};
-            fold4(w);
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            N += __shfl_xor(N, o, 64); S += __shfl_xor(S, o, 64); Q += __shfl_xor(Q, o, 64);
-        }
+        fold_loaded(v, P0, N, S, Q);
+        fold_entries<64, 4>(sg.e, sg.n_ent, lane + 64 * 4, P0, N, S, Q);
+        stat_wave_sum(N, S, Q);
         if (lane == 0) {
-            const double m = N > 0.0 ? S / N : 0.0;
-            double var = N > 0.0 ? Q / N - m * m : 0.0;
-            if (var < 0.0) var = 0.0;
-            shm[2 * wv] = (float)(P0 + m);
-            shm[2 * wv + 1] = (float)(1.0 / sqrt(var + (double)eps));
+            const float2 ms = stat_finish(N, S, Q, P0, eps);
+            shm[2 * wv] = ms.x;
+            shm[2 * wv + 1] = ms.y;
         }
         __syncthreads();
 #pragma unroll
         for (int k = 0; k < 8; ++k) { const int j = k >> (cpg == 4 ? 2 : 1); mu[k] = shm[2 * j]; rstd[k] = shm[2 * j + 1]; }
     } else {
-        const int cg0 = g * cpg;
-        const bool seg1 = cg0 >= os.c0;
-        const int slots = seg1 ? os.slots1 : os.slots0;
-        const int ush = seg1 ? os.ush1 : os.ush0;
-        const f32x4* e = seg1 ? os.p1 + ((long long)b * (os.c1 >> ush) + ((cg0 - os.c0) >> ush)) * slots
-                              : os.p0 + ((long long)b * (os.c0 >> ush) + (cg0 >> ush)) * slots;
-        const int n_ent = (cpg >> ush) * slots;
-        const float P0f = e[0].x;
+        const StatGroup sg = stat_group(os, b, g * cpg, cpg);
+        const float P0f = sg.e[0].x;
         double N = 0.0, S = 0.0, Q = 0.0;
         f32x4 v[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            v[k] = (int)threadIdx.x + 256 * k < n_ent ? e[threadIdx.x + 256 * k] : f32x4{0.f, 0.f, 0.f, 0.f};
+        load_entries<256, 4>(v, sg.e, sg.n_ent, threadIdx.x);
         issue_first();                                            // the x loads ride behind the first batch of entries
         const double P0 = (double)P0f;
-        auto fold4 = [&](const f32x4 (&w)[4]) {
+        fold_loaded(v, P0, N, S, Q);                              // straight-line: waits for the entries only (vmcnt(8))
+        fold_entries<256, 4>(sg.e, sg.n_ent, threadIdx.x + 256 * 4, P0, N, S, Q);   // > 1024 entries per group: 64 x 2048 images
+        stat_block_sum(sh, N, S, Q);
+        const float2 ms = stat_finish(N, S, Q, P0, eps);
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {                         // an absent entry (n = 0) adds nothing
-                const double n = w[k].y, d = (double)w[k].x - P0, s_ = w[k].z;
-                N += n;
-                S += s_ + n * d;
-                Q += (double)w[k].w + d * (2.0 * s_ + n * d);
-            }
-        };
-        fold4(v);                                                 // straight-line: waits for the entries only (vmcnt(8))
-        for (int base = threadIdx.x + 256 * 4; base < n_ent; base += 256 * 4) {   // > 1024 entries per group: 64 x 2048 images
-            f32x4 w[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                w[k] = base + 256 * k < n_ent ? e[base + 256 * k] : f32x4{0.f, 0.f, 0.f, 0.f};
-            fold4(w);
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            N += __shfl_xor(N, o, 64); S += __shfl_xor(S, o, 64); Q += __shfl_xor(Q, o, 64);
-        }
-        const int wv = threadIdx.x >> 6;
-        if ((threadIdx.x & 63) == 0) { sh[3 * wv] = N; sh[3 * wv + 1] = S; sh[3 * wv + 2] = Q; }
-        __syncthreads();
-        N = (sh[0] + sh[3]) + (sh[6] + sh[9]);
-        S = (sh[1] + sh[4]) + (sh[7] + sh[10]);
-        Q = (sh[2] + sh[5]) + (sh[8] + sh[11]);
-        const double m = N > 0.0 ? S / N : 0.0;
-        double var = N > 0.0 ? Q / N - m * m : 0.0;
-        if (var < 0.0) var = 0.0;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) { mu[k] = (float)(P0 + m); rstd[k] = (float)(1.0 / sqrt(var + (double)eps)); }
+        for (int k = 0; k < 8; ++k) { mu[k] = ms.x; rstd[k] = ms.y; }
     }
     // per channel: y = (x - mean) * A + Bc with A = rstd * gamma * (1 + scale), Bc = beta * (1 + scale) + shift -- the
     // form (and rounding order) of the convolutions' fused input norm (conv_f16x2_common.h gn_act)
@@ -721,9 +601,9 @@ extern "C" int lc_groupnorm_apply_os(const float* x, int64_t x_bs, const lc_oct_
                                      int act_silu, lc_stream_t s) {
     if (!x || !y || B <= 0 || G <= 0 || C % G) return LC_EINVAL;
     const int cpg = C / G;
-    OctStats2 os;
+    StatSegs os;
     // groups are whole entries (octets, quads, pairs or single channels: round 5) and lie inside one segment
-    if (const int rc = os_from_segments(s0, s1, C, cpg, os)) return rc;
+    if (const int rc = stat_segs_from(s0, s1, C, cpg, LC_EUNSUP, os)) return rc;
     const long long HW = (long long)H * W;
     int slabs = (int)((HW + 4095) / 4096);
     if (slabs < 1) slabs = 1;
@@ -743,49 +623,20 @@ extern "C" int lc_groupnorm_apply_os(const float* x, int64_t x_bs, const lc_oct_
 // Per-(sample, channel) rows (mu, A, Bc, 0) from the PRODUCER's statistics entries -- what gn_coeffs_kernel derives from the
 // partials of a statistics pass: y = (x - mu) * A + Bc.  One block per (group, sample): the fold of gn_apply_os_kernel, then
 // one row per channel of the group.  Consumer (round 6): the paired resampler of a resampling ResBlock (resample.hip).
-__global__ __launch_bounds__(256) void gn_coeffs_os_kernel(OctStats2 os, const float* __restrict__ gamma,
+__global__ __launch_bounds__(256) void gn_coeffs_os_kernel(StatSegs os, const float* __restrict__ gamma,
                                                           const float* __restrict__ beta, const float* __restrict__ scale,
                                                           const float* __restrict__ shift, long long ss_bs,
                                                           f32x4* __restrict__ out, int C, int Cpad, int G, float eps) {
     __shared__ double sh[12];
     const int g = blockIdx.x, b = blockIdx.y;
     const int cpg = C / G, cg0 = g * cpg;
-    const bool seg1 = cg0 >= os.c0;
-    const int slots = seg1 ? os.slots1 : os.slots0;
-    const int ush = seg1 ? os.ush1 : os.ush0;
-    const f32x4* e = seg1 ? os.p1 + ((long long)b * (os.c1 >> ush) + ((cg0 - os.c0) >> ush)) * slots
-                          : os.p0 + ((long long)b * (os.c0 >> ush) + (cg0 >> ush)) * slots;
-    const int n_ent = (cpg >> ush) * slots;
-    const double P0 = (double)e[0].x;
+    const StatGroup sg = stat_group(os, b, cg0, cpg);
+    const double P0 = (double)sg.e[0].x;
     double N = 0.0, S = 0.0, Q = 0.0;
-    for (int base = threadIdx.x; base < n_ent; base += 256 * 4) {
-        f32x4 v[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            v[k] = base + 256 * k < n_ent ? e[base + 256 * k] : f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const double n = v[k].y, d = (double)v[k].x - P0, s_ = v[k].z;
-            N += n;
-            S += s_ + n * d;
-            Q += (double)v[k].w + d * (2.0 * s_ + n * d);
-        }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        N += __shfl_xor(N, o, 64); S += __shfl_xor(S, o, 64); Q += __shfl_xor(Q, o, 64);
-    }
-    const int wv = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { sh[3 * wv] = N; sh[3 * wv + 1] = S; sh[3 * wv + 2] = Q; }
-    __syncthreads();
-    N = (sh[0] + sh[3]) + (sh[6] + sh[9]);
-    S = (sh[1] + sh[4]) + (sh[7] + sh[10]);
-    Q = (sh[2] + sh[5]) + (sh[8] + sh[11]);
-    const double m = N > 0.0 ? S / N : 0.0;
-    double var = N > 0.0 ? Q / N - m * m : 0.0;
-    if (var < 0.0) var = 0.0;
-    const float mu = (float)(P0 + m);
-    const float rstd = (float)(1.0 / sqrt(var + (double)eps));
+    fold_entries<256, 4>(sg.e, sg.n_ent, threadIdx.x, P0, N, S, Q);
+    stat_block_sum(sh, N, S, Q);
+    const float2 ms = stat_finish(N, S, Q, P0, eps);
+    const float mu = ms.x, rstd = ms.y;
     for (int k = threadIdx.x; k < cpg; k += 256) {
         const int c = cg0 + k;
         const float ga = gamma ? gamma[c] : 1.0f, be = beta ? beta[c] : 0.0f;
@@ -799,8 +650,8 @@ extern "C" int lc_groupnorm_coeffs_os(const lc_oct_stats* s0, const lc_oct_stats
                                       const float* scale, const float* shift, int64_t ss_bs, float* coeffs, int B, int C,
                                       int Cpad, int G, float eps, lc_stream_t s) {
     if (!coeffs || B <= 0 || G <= 0 || C % G || Cpad < C) return LC_EINVAL;
-    OctStats2 os;
-    if (const int rc = os_from_segments(s0, s1, C, C / G, os)) return rc;
+    StatSegs os;
+    if (const int rc = stat_segs_from(s0, s1, C, C / G, LC_EUNSUP, os)) return rc;
     hipLaunchKernelGGL(gn_coeffs_os_kernel, dim3(G, B), dim3(256), 0, lc_s(s), os, gamma, beta, scale, shift,
                        (long long)ss_bs, reinterpret_cast<f32x4*>(coeffs), C, Cpad, G, eps);
     return lc_launch_status();
@@ -835,7 +686,7 @@ extern "C" int lc_groupnorm_apply_split(const float* x, int64_t x_bs, const doub
     const long long HW = (long long)H * W;
     if (2ll * (C / 8) * HW * 16 >= (1ll << 31)) return LC_EUNSUP;       // 32-bit byte offsets into one sample's planes (as the consumer conv)
     const int nch = gn_chunks(B, G, (long long)(C / G) * HW);
-    OctStats2 os{nullptr, nullptr, 0, 0, 0, 0, 3, 3};
+    StatSegs os = STAT_SEGS_NONE;
     hipLaunchKernelGGL(gn_apply_split_kernel<0>, dim3(split_slabs(B, C, HW), C / 8, B), dim3(256), 0,
                        lc_s(s), x, (long long)x_bs, partials, os, gamma, beta, scale, shift,
                        (long long)ss_bs, reinterpret_cast<half8_t*>(y_split),
@@ -851,11 +702,11 @@ extern "C" int lc_groupnorm_apply_os_split(const float* x, int64_t x_bs, const l
                                            lc_stream_t s) {
     if (!x || !y_split || !range || B <= 0 || G <= 0 || C % G) return LC_EINVAL;
     const int cpg = C / G;
-    OctStats2 os;
-    if (const int rc = os_from_segments(s0, s1, C, cpg, os)) return rc;
+    StatSegs os;
+    if (const int rc = stat_segs_from(s0, s1, C, cpg, LC_EUNSUP, os)) return rc;
     // (a block of this kernel owns a channel OCTET: groups of whole octets -- one (mean, rstd) per block -- or 2 / 4
     // channels per group -- one group per wave --, whatever the entries' unit)
-    if ((cpg % 8 && cpg != 2 && cpg != 4) || os.c0 % 8 || C % 16) return LC_EUNSUP;
+    if ((cpg % 8 && cpg != 2 && cpg != 4) || os.seg[0].channels % 8 || C % 16) return LC_EUNSUP;
     const long long HW = (long long)H * W;
     if (2ll * (C / 8) * HW * 16 >= (1ll << 31)) return LC_EUNSUP;
     const dim3 grid(split_slabs(B, C, HW), C / 8, B);

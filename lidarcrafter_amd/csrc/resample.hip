@@ -5,6 +5,7 @@
 //   up:   per axis y[2i] = .25 x[i-1] + .75 x[i],  y[2i+1] = .75 x[i] + .25 x[i+1]
 // HBM-bound: one read of x (neighbours hit L1/L2), one write of y.
 #include "common.h"
+#include "stats_entry.h"
 
 namespace {
 
@@ -128,13 +129,14 @@ __global__ __launch_bounds__(256) void down2_vec_kernel(const float* __restrict_
             lc_st2(y2b + ((long long)c * Ho + i) * Wo + w0 / 2, o2);
         }
         if (ostats) {                                          // (uniform)
-            const float piv = lc_readfirstlane_f32(acc0);
-            const float d0 = acc0 - piv, d1 = acc1 - piv;
-            float s_ = d0 + d1, q_ = fmaf(d1, d1, d0 * d0);
+            StatAcc<PIVOT_FIRST> st;
+            st.start(acc0);
+            st.add2(acc0, acc1);
+            float s_ = st.s, q_ = st.q;
 #pragma unroll
             for (int sh = 32; sh > 0; sh >>= 1) { s_ += __shfl_xor(s_, sh, 64); q_ += __shfl_xor(q_, sh, 64); }
             if (lane == 0)
-                ostats[((long long)b * C + c) * ((long long)Ho * segs) + ((long long)i * segs + sg)] = f32x4{piv, 128.0f, s_, q_};
+                ostats[((long long)b * C + c) * ((long long)Ho * segs) + ((long long)i * segs + sg)] = f32x4{st.p, 128.0f, s_, q_};
         }
     }
 }

@@ -16,6 +16,7 @@
 // Also here: the plain fp32 -> pre-split pass (x * x_scale as fp16 hi / lo planes, no normalisation) for a low-resolution
 // operand that no GroupNorm apply pass writes (EfficientUNet's Block.upsample takes the block's output as it is).
 #include "common.h"
+#include "stats_entry.h"
 
 namespace {
 
@@ -213,19 +214,15 @@ __global__ __launch_bounds__(256) void up2_combine9_kernel(const float* __restri
             // (the next rows' loads stay in front of the 16-byte stores above, where the source has them: sunk behind the
             //  stores, one of them wrote a data register of the store right in front of it -- devtools/isa_store_audit.py)
             __builtin_amdgcn_sched_barrier(0);
-            const float piv = lc_readfirstlane_f32(top[0]);
-            float s_ = 0.0f, q_ = 0.0f;
+            StatAcc<PIVOT_FIRST> st;
+            st.start(top[0]);
 #pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                const float d0 = top[c] - piv, d1 = bot[c] - piv;
-                s_ += d0 + d1;
-                q_ = fmaf(d0, d0, q_);
-                q_ = fmaf(d1, d1, q_);
-            }
+            for (int c = 0; c < 4; ++c) st.add2(top[c], bot[c]);
+            float s_ = st.s, q_ = st.q;
 #pragma unroll
             for (int sh = 32; sh > 0; sh >>= 1) { s_ += __shfl_xor(s_, sh, 64); q_ += __shfl_xor(q_, sh, 64); }
             if (lane == 0)
-                ostats[((long long)b * Co + co) * ((long long)H * segs) + ((long long)i * segs + sg)] = f32x4{piv, 512.0f, s_, q_};
+                ostats[((long long)b * Co + co) * ((long long)H * segs) + ((long long)i * segs + sg)] = f32x4{st.p, 512.0f, s_, q_};
         }
         float Hn[3][4];
         horiz(Hn, i + 2 < H ? 1.0f : 0.0f);

@@ -218,7 +218,7 @@ def route_signature() -> tuple:
 # Default ON again since round 4.  (End of round 3 it was switched off: the entry was ONE 128-bit buffer store with
 # an SGPR soffset, and ~3 entries in 10^7 arrived with a foreign upper dword under the store pressure of the deferred
 # epilogue.  The entry is now ONE 32-bit store instruction in which the four lanes below the reducing lane carry one field
-# each (DefEpi::store_entry_lanes: the sum reaches lane R-1 by a DPP row_shl, pivot and count are uniform over lanes
+# each (store_entry_4lanes, stats_entry.h: the sum reaches lane R-1 by a DPP row_shl, pivot and count are uniform over lanes
 # R-3 .. R); devtools/entry_stress.py recomputes every entry of 10^8 per entry unit: 0 off, against 17 in 5e7 for the
 # old form on the same box -- profiles/r04_entry_store.txt.  Regression guard in the GPU suite:
 # tests/test_hip_parity.py::test_conv_statistics_entries_stress.)

@@ -50,7 +50,7 @@ def test_fold_matches_direct_statistics(C, G, units, split, offset):
     for grp in range(G):
         lo = grp * cpg
         c0, c1, u = next(sg for sg in segs if sg[0] <= lo < sg[1])
-        assert cpg % u == 0 and (lo - c0) % u == 0 and lo + cpg <= c1        # the kernels' preconditions (os_from_segments)
+        assert cpg % u == 0 and (lo - c0) % u == 0 and lo + cpg <= c1        # the kernels' preconditions (stat_segs_from, stats_entry.h)
         e = ent[c0][(lo - c0) // u:(lo - c0 + cpg) // u].reshape(-1, 4)
         mean, var = fold(e)
         ref = y[lo:lo + cpg].astype(np.float64)
