@@ -13,7 +13,7 @@ AT = np.array([[1, 1, 1, 0], [0, 1, -1, -1]], np.float64)
 
 
 def split(v, scale):
-    """split_pair of conv_f16x2.hip: hi = 11 significant bits, round toward zero; lo = fp16(s - hi)."""
+    """pair_split of csrc/f16x2.h: hi = 11 significant bits, round toward zero; lo = fp16(s - hi)."""
     s = (v * np.float32(scale)).astype(np.float32)
     hi = (s.view(np.uint32) & np.uint32(0xFFFFE000)).view(np.float32)
     lo = (s - hi).astype(np.float16).astype(np.float32)

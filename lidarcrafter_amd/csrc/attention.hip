@@ -12,11 +12,12 @@
 //      cross-half shuffle (lane ^ 32); the running max / sum / rescale are lane-local.
 //   O^T tile (32 ch x 32 queries):   A[i=c][k=key] = V[c][s],  B[k=key][j=query] = P^T[s][t]
 //   -> B is register r of the S^T accumulator as is: k-step r contracts keys
-//      kappa(r,half) = (r&3)+8*(r>>2)+4*half, and V is read from LDS with the same kappa.
+//      kappa(r,half) = mfma_row(r, half) of f16x2.h, and V is read from LDS with the same kappa.
 // Block = 4 waves x 32 queries of one head; K/V tiles of 32 keys staged in LDS.
 #include <cstdlib>
 
 #include "common.h"
+#include "attention_split.h"
 
 namespace {
 
@@ -29,10 +30,6 @@ struct AttnArgs {
     float* lse;    // optional [B * heads, Lq]: log2-sum-exp of the scaled scores (base 2, qscale included) for the backward pass
     const unsigned* qkv_amax;   // training entry (attn_h_kernel<..., PRE = true>): bit patterns of max |q|, |k|, |v| (attention_pre.h)
 };
-
-__device__ __forceinline__ const float* head_ptr(const lc_cm_operand& x, int b, int h) {
-    return x.p ? x.p + b * x.bs + h * x.hs : nullptr;
-}
 
 template <int DQK, int NDV>
 __global__ __launch_bounds__(256) void attn_kernel(AttnArgs a) {
@@ -117,7 +114,7 @@ __global__ __launch_bounds__(256) void attn_kernel(AttnArgs a) {
         float mt = -INFINITY;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int key = s0 + (r & 3) + 8 * (r >> 2) + 4 * kh;
+            const int key = s0 + mfma_row(r, kh);
             if (key >= Lk) sacc[r] = -INFINITY;
             mt = fmaxf(mt, sacc[r]);
         }
@@ -139,7 +136,7 @@ __global__ __launch_bounds__(256) void attn_kernel(AttnArgs a) {
         // ---- O^T += V P^T ---------------------------------------------------------------------
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int kap = (r & 3) + 8 * (r >> 2) + 4 * kh;
+            const int kap = mfma_row(r, kh);
 #pragma unroll
             for (int i = 0; i < NDV; ++i) {
                 const float av = vs[(i * 32 + l31) * VS + kap];
@@ -156,7 +153,7 @@ __global__ __launch_bounds__(256) void attn_kernel(AttnArgs a) {
         for (int i = 0; i < NDV; ++i)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int c = i * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh;
+                const int c = i * 32 + mfma_row(r, kh);
                 if (c < a.dv) lc_st(op + c * a.o_cs + t, oacc[i][r] * inv);
             }
     }
@@ -175,7 +172,6 @@ __global__ __launch_bounds__(256) void attn_kernel(AttnArgs a) {
 //        A = V unit [step][half][c] holding V[c][kappa(8*step + 0..7, half)] -- the staging
 //        pass writes each thread's 8 consecutive keys as two 8-byte pieces into that order.
 // K/V of the next tile are prefetched into registers while the current tile is computed.
-#include "attention_split.h"
 #include "attention_pre.h"
 
 // NW = waves per block (32 queries each).  4: the block of rounds 1-4.  8 (round 5): the K / V staging of a tile is
@@ -217,7 +213,7 @@ __global__ __launch_bounds__(64 * NW) void attn_h_kernel(AttnArgs a) {
                 }
                 v[j] = val;
             }
-            split8(v, qs, qh[st], ql[st]);
+            split8_skip1(v, qs, qh[st], ql[st]);
         }
     }
     f32x16 oacc[NDV];
@@ -319,13 +315,13 @@ __global__ __launch_bounds__(64 * NW) void attn_h_kernel(AttnArgs a) {
     auto store_tile = [&]() {
         if (tid < NKU) {
             half8 hi, lo;
-            split8(kreg, k_pre, hi, lo);
+            split8_skip1(kreg, k_pre, hi, lo);
             k_hi[tid] = hi;                       // unit index = cb*32 + key = tid
             k_lo[tid] = lo;
         }
         if (v_role) {
             half8 hi, lo;
-            split8(vreg, v_pre, hi, lo);
+            split8_skip1(vreg, v_pre, hi, lo);
             // keys 8o+0..3 -> (step o>>1, half 0), keys 8o+4..7 -> (step o>>1, half 1); both land
             // in the 4-element piece (o&1) of their unit
             const int u0 = ((v_o >> 1) * 2 + 0) * DV + v_c, u1 = u0 + DV;
@@ -356,6 +352,7 @@ __global__ __launch_bounds__(64 * NW) void attn_h_kernel(AttnArgs a) {
         for (int st = 0; st < NST; ++st) {
             const half8 ah = k_hi[(2 * st + kh) * 32 + l31];
             const half8 al = k_lo[(2 * st + kh) * 32 + l31];
+            // (the triple product of f16x2.h, written out: through f16x2_mma this kernel's registers are allocated differently)
             sacc = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, qh[st], sacc, 0, 0, 0);
             sacc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, ql[st], sacc, 0, 0, 0);
             sacc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, qh[st], sacc, 0, 0, 0);
@@ -364,7 +361,7 @@ __global__ __launch_bounds__(64 * NW) void attn_h_kernel(AttnArgs a) {
         if (s0 + 32 > Lk) {    // ragged last tile (uniform branch)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int key = s0 + (r & 3) + 8 * (r >> 2) + 4 * kh;
+                const int key = s0 + mfma_row(r, kh);
                 if (key >= Lk) sacc[r] = -INFINITY;
             }
         }
@@ -404,7 +401,7 @@ __global__ __launch_bounds__(64 * NW) void attn_h_kernel(AttnArgs a) {
             for (int i = 0; i < NDV; ++i) {
                 const half8 avh = v_hi[(st * 2 + kh) * DV + i * 32 + l31];
                 const half8 avl = v_lo[(st * 2 + kh) * DV + i * 32 + l31];
-                oacc[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(avl, ph, oacc[i], 0, 0, 0);
+                oacc[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(avl, ph, oacc[i], 0, 0, 0);      // (written out, as above)
                 oacc[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(avh, pl, oacc[i], 0, 0, 0);
                 oacc[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(avh, ph, oacc[i], 0, 0, 0);
             }
@@ -419,7 +416,7 @@ __global__ __launch_bounds__(64 * NW) void attn_h_kernel(AttnArgs a) {
         for (int i = 0; i < NDV; ++i)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int c = i * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh;
+                const int c = i * 32 + mfma_row(r, kh);
                 if (c < a.dv) lc_st(op + c * a.o_cs + t, oacc[i][r] * inv);
             }
     }

@@ -14,12 +14,13 @@
 //   dS    = scale * P (dP - D[t])
 //   dq[c][t] = sum_s k[c][s] dS[s][t]    dk[c][s] = sum_t q[c][t] dS[s][t]    dv[c][s] = sum_t do[c][t] P[s][t]
 // Two kernels, both with the register trick of attention.hip: an S tile's accumulator register r of a lane IS the
-// B operand of the next product's k-step r (rows kappa(r, half) = (r & 3) + 8 (r >> 2) + 4 half).
+// B operand of the next product's k-step r (rows kappa(r, half) = mfma_row(r, half) of f16x2.h).
 //   attn_bwd_dq_kernel   block = 4 waves x 32 queries, loops over 32-key tiles (K, V staged in LDS):
 //                        S^T = K^T Q, dP^T = V^T dO (lane = query: lse, D lane-local), dQ^T += K dS^T
 //   attn_bwd_dkv_kernel  block = 4 waves x 32 keys, loops over 32-query tiles (Q, dO, lse, D staged in LDS):
 //                        S = Q^T K, dV^T += dO P, dP = dO^T V, dK^T += Q dS
 #include "common.h"
+#include "f16x2.h"      // mfma_row
 
 namespace {
 
@@ -31,8 +32,6 @@ struct AttnBwdArgs {
 };
 
 constexpr int TS = 33;   // LDS row stride of a 32-wide tile: conflict-free along rows and along columns
-
-__device__ __forceinline__ int kappa(int r, int kh) { return (r & 3) + 8 * (r >> 2) + 4 * kh; }
 
 // D[bh][t] = sum_c do[c][t] * o[c][t]
 __global__ __launch_bounds__(256) void attn_dsum_kernel(const float* __restrict__ o, const float* __restrict__ dout,
@@ -102,13 +101,13 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(AttnBwdArgs a) {
         float ds[16];
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int key = s0 + kappa(r, kh);
+            const int key = s0 + mfma_row(r, kh);
             const float p = key < a.Lk ? exp2f(fmaf(sacc[r], a.qscale, -lse_t)) : 0.f;
             ds[r] = p * (dpacc[r] - d_t) * a.scale;
         }
 #pragma unroll
         for (int r = 0; r < 16; ++r) {            // dQ^T += K dS^T: A[i = c][k = key kappa] = K, B = dS register r
-            const int kap = kappa(r, kh);
+            const int kap = mfma_row(r, kh);
 #pragma unroll
             for (int i = 0; i < NDQ; ++i)
                 dqacc[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(ks[(i * 32 + l31) * TS + kap], ds[r], dqacc[i], 0, 0, 0);
@@ -120,7 +119,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(AttnBwdArgs a) {
         for (int i = 0; i < NDQ; ++i)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int c = i * 32 + kappa(r, kh);
+                const int c = i * 32 + mfma_row(r, kh);
                 if (c < a.dqk) dqb[(long long)c * a.Lq + t] = dqacc[i][r];
             }
     }
@@ -191,13 +190,13 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(AttnBwdArgs a) {
         float p[16], ds[16];
 #pragma unroll
         for (int r = 0; r < 16; ++r) {            // row = query kappa(r, half) of the tile, column = this lane's key
-            const int tq = kappa(r, kh);
+            const int tq = mfma_row(r, kh);
             p[r] = (sok && t0 + tq < a.Lq) ? exp2f(fmaf(sacc[r], a.qscale, -lse_s[tq])) : 0.f;
             ds[r] = p[r] * (dpacc[r] - d_s[tq]) * a.scale;
         }
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int kap = kappa(r, kh);
+            const int kap = mfma_row(r, kh);
 #pragma unroll
             for (int i = 0; i < NDV; ++i)         // dV^T += dO P: A[i = c][k = query kappa] = dO, B = P register r
                 dvacc[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(dos[(i * 32 + l31) * TS + kap], p[r], dvacc[i], 0, 0, 0);
@@ -213,14 +212,14 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(AttnBwdArgs a) {
         for (int i = 0; i < NDQ; ++i)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int c = i * 32 + kappa(r, kh);
+                const int c = i * 32 + mfma_row(r, kh);
                 if (c < a.dqk) dkb[(long long)c * a.Lk + s] = dkacc[i][r];
             }
 #pragma unroll
         for (int i = 0; i < NDV; ++i)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int c = i * 32 + kappa(r, kh);
+                const int c = i * 32 + mfma_row(r, kh);
                 if (c < a.dv_) dvb[(long long)c * a.Lk + s] = dvacc[i][r];
             }
     }

@@ -8,7 +8,7 @@
 //   channel units  X_c[cb][pos]        = X[8 cb + 0..7][pos]                    products that contract over channels
 //   position units X_p[step][half][c]  = X[c][kappa(8 step + 0..7, half)]       products that contract over keys / queries:
 //                                        their B operand is the previous product's accumulator registers 8 step .. 8 step + 7
-//                                        (kappa(r, half) = (r & 3) + 8 (r >> 2) + 4 half), split in registers
+//                                        (kappa(r, half) = mfma_row(r, half) of f16x2.h), split in registers
 // dQ kernel   (block = 4 waves x 32 queries; per 32-key tile: K_c, K_p, V_c staged):
 //     S^T = K_c Q, dP^T = V_c dO, dS^T = scale P (dP - D) in registers, dQ^T += K_p dS^T
 // dK/dV kernel (block = 4 waves x 32 keys; per 32-query tile: Q_c, Q_p, dO_c, dO_p, lse, D staged):
@@ -18,15 +18,11 @@
 // the constant 16, which saturated |x| >= 4094 silently); dO is a gradient of arbitrary magnitude: attn_dsum_h_kernel measures max |dO| next to D and every block derives the power of two that puts
 // it at 2^6, so dP, dS and the outputs carry that factor exactly until the epilogue divides it out.
 #include "common.h"
+#include "attention_split.h"      // P_PRE; the split: f16x2.h
 
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-
 #include "attention_pre.h"
-
-constexpr float P_PRE = 2048.0f;
 
 struct AttnBwdHArgs {
     const float *q, *k, *v, *dout, *lse, *dsum;
@@ -37,23 +33,6 @@ struct AttnBwdHArgs {
     float qscale, scale;
 };
 
-__device__ __forceinline__ int kappa(int r, int kh) { return (r & 3) + 8 * (r >> 2) + 4 * kh; }
-
-// the split rule of the forward kernel: s = v * scale, hi = 11 significant bits (truncated), lo = fp16(s - hi)
-__device__ __forceinline__ void split8(const float (&v)[8], float scale, half8& hi, half8& lo) {
-    typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-    typedef float f2 __attribute__((ext_vector_type(2)));
-#pragma unroll
-    for (int k = 0; k < 8; k += 2) {
-        const float s0 = v[k] * scale, s1 = v[k + 1] * scale;
-        const float h0 = __uint_as_float(__float_as_uint(s0) & 0xFFFFE000u);
-        const float h1 = __uint_as_float(__float_as_uint(s1) & 0xFFFFE000u);
-        const h2 ph = __builtin_bit_cast(h2, __builtin_amdgcn_cvt_pkrtz(h0, h1));
-        f2 r; r.x = s0 - h0; r.y = s1 - h1;
-        const h2 pl = __builtin_convertvector(r, h2);
-        hi[k] = ph.x; hi[k + 1] = ph.y; lo[k] = pl.x; lo[k + 1] = pl.y;
-    }
-}
 
 // the power of two that puts max |dO| into [2^6, 2^7)
 __device__ __forceinline__ float do_scale_from(unsigned amax_bits) {
@@ -115,6 +94,8 @@ __device__ __forceinline__ void store_poct(half8* u_hi, half8* u_lo, const float
     *l1 = __builtin_shufflevector(lo, lo, 4, 5, 6, 7);
 }
 
+// The triple product of f16x2.h (f16x2_mma) as a macro: its A operands are LDS reads, which the macro names twice; read
+// once, through the function, eight of the ten kernels come out with other registers and schedules.
 #define LC_MFMA3(ACC, AH, AL, BH, BL)                                           \
     do {                                                                        \
         ACC = __builtin_amdgcn_mfma_f32_32x32x16_f16(AL, BH, ACC, 0, 0, 0);     \
@@ -199,7 +180,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_h_kernel(AttnBwdHArgs a) {
         float ds[16];
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int key = s0 + kappa(r, kh);
+            const int key = s0 + mfma_row(r, kh);
             const float p = key < a.Lk ? __builtin_amdgcn_exp2f(fmaf(sacc[r], S_UN, -lse_t)) : 0.f;
             ds[r] = p * (dpacc[r] * c2 - d_t) * a.scale;        // = sdo * dS
         }
@@ -222,7 +203,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_h_kernel(AttnBwdHArgs a) {
         for (int i = 0; i < NDQ; ++i)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int c = i * 32 + kappa(r, kh);
+                const int c = i * 32 + mfma_row(r, kh);
                 if (c < a.dqk) dqb[(long long)c * a.Lq + t] = dqacc[i][r] * un;
             }
     }
@@ -310,7 +291,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_h_kernel(AttnBwdHArgs a) {
         float p[16], ds[16];
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int tq = kappa(r, kh);
+            const int tq = mfma_row(r, kh);
             p[r] = (sok && t0 + tq < a.Lq) ? __builtin_amdgcn_exp2f(fmaf(sacc[r], c1, -lse_s[tq])) : 0.f;
             ds[r] = p[r] * (dpacc[r] * c2 - d_s[tq]) * a.scale;      // = sdo * dS
         }
@@ -340,18 +321,19 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_h_kernel(AttnBwdHArgs a) {
         for (int i = 0; i < NDQ; ++i)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int c = i * 32 + kappa(r, kh);
+                const int c = i * 32 + mfma_row(r, kh);
                 if (c < a.dqk) dkb[(long long)c * a.Lk + s] = dkacc[i][r] * unk;
             }
 #pragma unroll
         for (int i = 0; i < NDV; ++i)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int c = i * 32 + kappa(r, kh);
+                const int c = i * 32 + mfma_row(r, kh);
                 if (c < a.dv_) dvb[(long long)c * a.Lk + s] = dvacc[i][r] * unv;
             }
     }
 }
+
 #undef LC_MFMA3
 
 }  // namespace

@@ -1,7 +1,7 @@
 // Range-safe pre-scales of the TRAINING attention's f16x2 operands (round 6).
 // q, k, v are multiplied by a power of two before their fp16 hi / lo split.  Rounds 1-5 used the constant 16: exact for
-// activations of a normalised network, but |x| >= 4094 saturates the hi half silently (cvt_pkrtz saturates, it does not
-// produce inf) and |x| << 1 loses the lo half.  The training entry points now measure max |q|, max |k|, max |v| on the
+// activations of a normalised network, but |x| >= 4094 saturates the hi half silently (the toward-zero pack of f16x2.h saturates, it does
+// not produce inf) and |x| << 1 loses the lo half.  The training entry points now measure max |q|, max |k|, max |v| on the
 // device (attn_amax3_kernel: no host synchronisation -- a backward pass cannot be repeated after a host-side poll) and
 // every kernel derives its pre-scales from those three words with the rule below: 16 while max |x| * 16 lies in
 // [2^2, 2^15) -- results of typical networks stay bit-identical -- otherwise the power of two that puts max |x| * pre into

@@ -31,10 +31,6 @@ struct UArgs {
     float qscale;
 };
 
-__device__ __forceinline__ const float* head_ptr(const lc_cm_operand& x, int b, int h) {
-    return x.p ? x.p + b * x.bs + h * x.hs : nullptr;
-}
-
 template <int NW>
 __global__ __launch_bounds__(64 * NW) void attn_u_kernel(UArgs a) {
     constexpr int NST = 4;
@@ -63,7 +59,7 @@ __global__ __launch_bounds__(64 * NW) void attn_u_kernel(UArgs a) {
                 }
                 v[j] = val;
             }
-            split8(v, qs, qh[st], ql[st]);
+            split8_skip1(v, qs, qh[st], ql[st]);
         }
     }
     f32x16 oacc;
@@ -108,15 +104,13 @@ __global__ __launch_bounds__(64 * NW) void attn_u_kernel(UArgs a) {
         }
 #pragma unroll
         for (int st = 0; st < NST; ++st) {
-            sacc = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[st], qh[st], sacc, 0, 0, 0);
-            sacc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[st], ql[st], sacc, 0, 0, 0);
-            sacc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[st], qh[st], sacc, 0, 0, 0);
+            sacc = f16x2_mma(sacc, ah[st], al[st], qh[st], ql[st]);      // one accumulator, three products back to back
         }
         // ---- online softmax (base 2) ------------------------------------------------------------
         if (s0 + 32 > a.Lk) {    // ragged last tile (uniform branch)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int key = s0 + (r & 3) + 8 * (r >> 2) + 4 * kh;
+                const int key = s0 + mfma_row(r, kh);
                 if (key >= a.Lk) sacc[r] = -INFINITY;
             }
         }
@@ -148,9 +142,7 @@ __global__ __launch_bounds__(64 * NW) void attn_u_kernel(UArgs a) {
             for (int j = 0; j < 8; ++j) pv[j] = p[8 * st + j];
             half8 ph, pl;
             split8(pv, 1.0f, ph, pl);
-            oacc = __builtin_amdgcn_mfma_f32_32x32x16_f16(avl[st], ph, oacc, 0, 0, 0);
-            oacc = __builtin_amdgcn_mfma_f32_32x32x16_f16(avh[st], pl, oacc, 0, 0, 0);
-            oacc = __builtin_amdgcn_mfma_f32_32x32x16_f16(avh[st], ph, oacc, 0, 0, 0);
+            oacc = f16x2_mma(oacc, avh[st], avl[st], ph, pl);
         }
     }
     const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
@@ -159,7 +151,7 @@ __global__ __launch_bounds__(64 * NW) void attn_u_kernel(UArgs a) {
     if (t < a.Lq) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int c = (r & 3) + 8 * (r >> 2) + 4 * kh;
+            const int c = mfma_row(r, kh);
             if (c < a.dv) lc_st(op + c * a.o_cs + t, oacc[r] * inv);
         }
     }

@@ -61,6 +61,22 @@ __device__ __forceinline__ void lc_st4(__amdgpu_buffer_rsrc_t rs, unsigned byte_
 // GroupNorm apply passes, which are VALU-bound, not HBM-bound (profiles/r05_level0.txt section 7).
 __device__ __forceinline__ float lc_silu(float v) { return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v)); }
 
+// exact (erf) GELU: the gate of HDiT's GEGLU, forward (hdit.hip) and backward (hdit_bwd.hip)
+__device__ __forceinline__ float gelu_erf(float g) { return 0.5f * g * (1.0f + erff(g * 0.70710678118654752f)); }
+
+// The chunking of the GroupNorm statistics partials (lc_groupnorm_stats of norm.hip; the JVP statistics of flow_jvp.hip form
+// their first two partials over the same spans in the same order).
+// elements per statistics block: 64 KiB normally, 16 KiB when the tensor is so small that 64 KiB
+// blocks would leave most CUs idle (deep levels at small batch: 128 blocks for [8,512,4,128])
+__host__ __device__ inline int gn_chunk_elems(int B, int G, long long n) {
+    const long long blocks = (long long)B * G * ((n + 16383) / 16384);
+    return blocks >= 512 ? 16384 : 4096;
+}
+__host__ __device__ inline int gn_chunks(int B, int G, long long n) {
+    const int ce = gn_chunk_elems(B, G, n);
+    return (int)((n + ce - 1) / ce);
+}
+
 // A lane's float as a wave-uniform value.  __builtin_amdgcn_readlane / readfirstlane take and return `int`: handed a
 // float they CONVERT it, and the "pivot" of a statistics entry came back truncated to an integer -- up to 1 away from
 // every value it was meant to sit among (tests/test_gn_structured.py).  The bits go through unchanged here.

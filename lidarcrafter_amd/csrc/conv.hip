@@ -17,6 +17,7 @@
 // K loop: chunks of CK input channels; chunk c+1 is prefetched global->registers while the
 // MFMAs of chunk c run from LDS (register-staged double buffering, one LDS buffer).
 #include "common.h"
+#include "f16x2.h"      // mfma_row
 
 namespace {
 
@@ -191,7 +192,7 @@ __global__ __launch_bounds__(256, 2) void conv_ring_kernel(ConvArgs a) {
         for (int i = 0; i < C::TCO_; ++i) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int co = co0 + (wco * C::TCO_ + i) * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh;
+                const int co = mfma_row(r, kh, co0 + (wco * C::TCO_ + i) * 32);
                 if (pok && co < a.Co) {
                     float v = acc[i][j][r];
                     if (a.bias) v += a.bias[co];

@@ -13,6 +13,7 @@
 // channel tile, each writing its partial sums, and a second kernel adds the partials in index
 // order (deterministic, no atomics).
 #include "common.h"
+#include "f16x2.h"
 
 namespace {
 
@@ -150,7 +151,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(const float* __restr
     for (int t = 0; t < NTAP; ++t)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int co = co0 + wco * 32 + (r & 3) + 8 * (r >> 2) + 4 * kk;
+            const int co = mfma_row(r, kk, co0 + wco * 32);
             const int ci = ci0 + wci * 32 + l31;
             if (co < Co && ci < Ci) pp[((long long)co * Ci + ci) * NTAP + t] = acc[t][r];
         }
@@ -171,26 +172,6 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(const float* __restr
 // Tile = 2 image rows x 32 columns (K = 64 pixels, 4 MFMA k-steps), block = 4 waves on a 64 co x 64 ci
 // channel tile with one accumulator per tap; LDS 68 KB (3x3) -> two blocks per CU, and the next
 // tile's global loads are in flight (registers) while the current one is contracted.
-typedef _Float16 half8_w __attribute__((ext_vector_type(8)));
-typedef _Float16 half4_w __attribute__((ext_vector_type(4)));
-typedef _Float16 half2_w __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4_w __attribute__((ext_vector_type(4)));
-typedef float f32x2_w __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ void split4(const f32x4 v, float sc, half4_w& hi, half4_w& lo) {
-    const float s0 = v.x * sc, s1 = v.y * sc, s2 = v.z * sc, s3 = v.w * sc;
-    const float h0 = __uint_as_float(__float_as_uint(s0) & 0xFFFFE000u);
-    const float h1 = __uint_as_float(__float_as_uint(s1) & 0xFFFFE000u);
-    const float h2 = __uint_as_float(__float_as_uint(s2) & 0xFFFFE000u);
-    const float h3 = __uint_as_float(__float_as_uint(s3) & 0xFFFFE000u);
-    const half2_w a = __builtin_bit_cast(half2_w, __builtin_amdgcn_cvt_pkrtz(h0, h1));
-    const half2_w b = __builtin_bit_cast(half2_w, __builtin_amdgcn_cvt_pkrtz(h2, h3));
-    f32x2_w r0 = {s0 - h0, s1 - h1}, r1 = {s2 - h2, s3 - h3};
-    const half2_w c = __builtin_convertvector(r0, half2_w), d = __builtin_convertvector(r1, half2_w);
-    hi = half4_w{a.x, a.y, b.x, b.y};
-    lo = half4_w{c.x, c.y, d.x, d.y};
-}
-
 template <int KS>
 __global__ __launch_bounds__(256, 2) void conv_wgrad_h_kernel(
     const float* __restrict__ x, long long x_bs, const float* __restrict__ dy, long long dy_bs,
@@ -258,27 +239,25 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_h_kernel(
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int e = tid + i * 256, c = e >> 4, r = (e >> 3) & 1, q = e & 7;
-            half4_w hi, lo;
+            half4 hi, lo;
             split4(dv[i], sdy, hi, lo);
-            *reinterpret_cast<half4_w*>(ds_h + c * DS + r * TWX + 4 * q) = hi;
-            *reinterpret_cast<half4_w*>(ds_l + c * DS + r * TWX + 4 * q) = lo;
+            *reinterpret_cast<half4*>(ds_h + c * DS + r * TWX + 4 * q) = hi;
+            *reinterpret_cast<half4*>(ds_l + c * DS + r * TWX + 4 * q) = lo;
         }
 #pragma unroll
         for (int i = 0; i < NXV; ++i) {
             const int e = tid + i * 256, c = e / (XR * 8), rem = e - c * (XR * 8), r = rem >> 3, q = rem & 7;
-            half4_w hi, lo;
+            half4 hi, lo;
             split4(xv[i], sx, hi, lo);
-            *reinterpret_cast<half4_w*>(xs_h + c * CS + r * RS + XOFF + 4 * q) = hi;
-            *reinterpret_cast<half4_w*>(xs_l + c * CS + r * RS + XOFF + 4 * q) = lo;
+            *reinterpret_cast<half4*>(xs_h + c * CS + r * RS + XOFF + 4 * q) = hi;
+            *reinterpret_cast<half4*>(xs_l + c * CS + r * RS + XOFF + 4 * q) = lo;
         }
 #pragma unroll
         for (int i = 0; i < NHV; ++i) {
             const int e = tid + i * 256, c = e / (XR * 2), rem = e - c * (XR * 2), r = rem >> 1, side = rem & 1;
             const float sv = hv[i] * sx;
-            const float hf = __uint_as_float(__float_as_uint(sv) & 0xFFFFE000u);
             const int d = c * CS + r * RS + (side ? XOFF + TWX : XOFF - 1);
-            xs_h[d] = (_Float16)hf;
-            xs_l[d] = (_Float16)(sv - hf);
+            f16x2_split_scalar(sv, xs_h[d], xs_l[d]);
         }
     };
     int tile = split;
@@ -295,20 +274,18 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_h_kernel(
 #pragma unroll 1   // (unrolled, hipcc hoists every fragment of the four k-steps: 259 spilled registers)
         for (int s = 0; s < 4; ++s) {
             const int r = s >> 1, px0 = (s & 1) * 16;
-            const half8_w ah = *reinterpret_cast<const half8_w*>(ahp + r * TWX + px0);
-            const half8_w al = *reinterpret_cast<const half8_w*>(alp + r * TWX + px0);
+            const half8 ah = *reinterpret_cast<const half8*>(ahp + r * TWX + px0);
+            const half8 al = *reinterpret_cast<const half8*>(alp + r * TWX + px0);
 #pragma unroll
             for (int ky = 0; ky < KS; ++ky) {
                 __builtin_amdgcn_sched_barrier(0);
                 const _Float16* ph = bhp + (r + ky) * RS + px0;
                 const _Float16* pl = blp + (r + ky) * RS + px0;
-                const u32x4_w mh = *reinterpret_cast<const u32x4_w*>(ph);
-                const u32x4_w ml = *reinterpret_cast<const u32x4_w*>(pl);
+                const lc_u32x4 mh = *reinterpret_cast<const lc_u32x4*>(ph);
+                const lc_u32x4 ml = *reinterpret_cast<const lc_u32x4*>(pl);
                 if constexpr (KS == 1) {
-                    const half8_w bh = __builtin_bit_cast(half8_w, mh), bl = __builtin_bit_cast(half8_w, ml);
-                    acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acc[0], 0, 0, 0);
-                    acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acc[0], 0, 0, 0);
-                    acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc[0], 0, 0, 0);
+                    const half8 bh = __builtin_bit_cast(half8, mh), bl = __builtin_bit_cast(half8, ml);
+                    acc[0] = f16x2_mma(acc[0], ah, al, bh, bl);      // one accumulator, three products back to back
                 } else {
                     const unsigned Lh = *reinterpret_cast<const unsigned*>(ph - 2);
                     const unsigned Rh = *reinterpret_cast<const unsigned*>(ph + 8);
@@ -318,20 +295,18 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_h_kernel(
                                    h23 = __builtin_amdgcn_alignbit(mh.w, mh.z, 16);
                     const unsigned l01 = __builtin_amdgcn_alignbit(ml.y, ml.x, 16), l12 = __builtin_amdgcn_alignbit(ml.z, ml.y, 16),
                                    l23 = __builtin_amdgcn_alignbit(ml.w, ml.z, 16);
-                    const u32x4_w lh = {__builtin_amdgcn_alignbit(mh.x, Lh, 16), h01, h12, h23};
-                    const u32x4_w ll = {__builtin_amdgcn_alignbit(ml.x, Ll, 16), l01, l12, l23};
-                    const u32x4_w rh = {h01, h12, h23, __builtin_amdgcn_alignbit(Rh, mh.w, 16)};
-                    const u32x4_w rl = {l01, l12, l23, __builtin_amdgcn_alignbit(Rl, ml.w, 16)};
-                    const half8_w bh[3] = {__builtin_bit_cast(half8_w, lh), __builtin_bit_cast(half8_w, mh),
-                                           __builtin_bit_cast(half8_w, rh)};
-                    const half8_w bl[3] = {__builtin_bit_cast(half8_w, ll), __builtin_bit_cast(half8_w, ml),
-                                           __builtin_bit_cast(half8_w, rl)};
+                    const lc_u32x4 lh = {__builtin_amdgcn_alignbit(mh.x, Lh, 16), h01, h12, h23};
+                    const lc_u32x4 ll = {__builtin_amdgcn_alignbit(ml.x, Ll, 16), l01, l12, l23};
+                    const lc_u32x4 rh = {h01, h12, h23, __builtin_amdgcn_alignbit(Rh, mh.w, 16)};
+                    const lc_u32x4 rl = {l01, l12, l23, __builtin_amdgcn_alignbit(Rl, ml.w, 16)};
+                    const half8 bh[3] = {__builtin_bit_cast(half8, lh), __builtin_bit_cast(half8, mh),
+                                           __builtin_bit_cast(half8, rh)};
+                    const half8 bl[3] = {__builtin_bit_cast(half8, ll), __builtin_bit_cast(half8, ml),
+                                           __builtin_bit_cast(half8, rl)};
 #pragma unroll
                     for (int kx = 0; kx < 3; ++kx) {
                         const int t = ky * 3 + kx;
-                        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh[kx], acc[t], 0, 0, 0);
-                        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl[kx], acc[t], 0, 0, 0);
-                        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh[kx], acc[t], 0, 0, 0);
+                        acc[t] = f16x2_mma(acc[t], ah, al, bh[kx], bl[kx]);
                     }
                 }
             }
@@ -344,7 +319,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_h_kernel(
     for (int t = 0; t < NTAP; ++t)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int co = co0 + wco * 32 + (r & 3) + 8 * (r >> 2) + 4 * kk;
+            const int co = mfma_row(r, kk, co0 + wco * 32);
             const int ci = ci0 + wci * 32 + l31;
             if (co < Co && ci < Ci) pp[((long long)t * Co + co) * Ci + ci] = acc[t][r];
         }

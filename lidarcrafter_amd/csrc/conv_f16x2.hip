@@ -12,8 +12,7 @@
 // reads it after the forward / sampling run: a value >= 2^15 (or so small that the lo halves are
 // all subnormal) re-derives the layer's x_scale (target 2^12, sixteen-fold headroom) and the
 // forward is re-run -- a result computed from saturated operands is never handed out silently.
-// Both kernels use ONE split rule (split_pair below): hi = s truncated to 11 significant bits and
-// packed round-toward-zero (saturates at 65504, never inf), lo = fp16(s - hi).
+// Both kernels use ONE split rule, the one every MFMA kernel of the project uses: f16x2.h.
 // Per-product relative error ~5e-7 (fp32 rounding: 6e-8) at 3/16 of the fp32-MFMA instruction
 // cost: 16x rate / 3 passes = 5.3x the fp32 matrix peak.
 //
@@ -205,11 +204,7 @@ __global__ __launch_bounds__(256, (C::BN > 64 && C::NTAP == 9) ? 1 : 2) void con
                 for (int i = 0; i < C::TCO_; ++i)
 #pragma unroll
                     for (int j = 0; j < C::TPX_; ++j) {
-                        if (LC_F16X2_TERMS & 2)
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[i], bh[j], acc[i][j], 0, 0, 0);
-                        if (LC_F16X2_TERMS & 4)
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bl[j], acc[i][j], 0, 0, 0);
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bh[j], acc[i][j], 0, 0, 0);
+                        acc[i][j] = f16x2_mma<LC_F16X2_TERMS>(acc[i][j], ah[i], al[i], bh[j], bl[j]);   // back to back per accumulator
                     }
             }
         }
@@ -241,7 +236,7 @@ __global__ __launch_bounds__(256, (C::BN > 64 && C::NTAP == 9) ? 1 : 2) void con
     for (int i = 0; i < C::TCO_; ++i)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int co = co_wave + i * 32 + (r & 3) + 8 * (r >> 2);
+            const int co = mfma_row(r, 0, co_wave + i * 32);
             bias_r[i][r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_b, (unsigned)co * 4u, 0, 0));
         }
     StatAcc<PIVOT_WAVE> st[C::TCO_][4];
@@ -259,7 +254,7 @@ __global__ __launch_bounds__(256, (C::BN > 64 && C::NTAP == 9) ? 1 : 2) void con
         for (int i = 0; i < C::TCO_; ++i)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int cor = i * 32 + (r & 3) + 8 * (r >> 2);
+                const int cor = mfma_row(r, 0, i * 32);
                 res_r[i][r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
                     rs_r, co_wave + cor < a.Co ? vo : OOB, (unsigned)cor * HW4, 0));
             }
@@ -267,7 +262,7 @@ __global__ __launch_bounds__(256, (C::BN > 64 && C::NTAP == 9) ? 1 : 2) void con
         for (int i = 0; i < C::TCO_; ++i) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int cor = i * 32 + (r & 3) + 8 * (r >> 2);
+                const int cor = mfma_row(r, 0, i * 32);
                 float v = acc[i][j][r] * out_unscale;
                 v += bias_r[i][r];
                 v += res_r[i][r];
@@ -500,21 +495,21 @@ __global__ __launch_bounds__(C::NT, C::NT / 256) void conv_f16x2_pipe_kernel(Con
     };
     auto stage_pair = [&](float (&xr)[NXU][8], int i, int q, const f32x4 row) {
         if (LC_ABLATE & 1) { asm volatile("" ::"v"(xr[i][2 * q]), "v"(xr[i][2 * q + 1])); return; }
-        h2_t ph, pl;
+        half2v ph, pl;
         if constexpr (GNM != 0) {
-            f2_t v = {xr[i][2 * q], xr[i][2 * q + 1]};
-            const f2_t A = {row.x, row.y}, Bv = {row.z, row.w};
+            f32x2 v = {xr[i][2 * q], xr[i][2 * q + 1]};
+            const f32x2 A = {row.x, row.y}, Bv = {row.z, row.w};
             v = __builtin_elementwise_fma(v, A, Bv);
             if constexpr (GNM == 1) {
-                const f2_t t = v * silu_c;
-                f2_t e = {__builtin_amdgcn_exp2f(t.x), __builtin_amdgcn_exp2f(t.y)};
+                const f32x2 t = v * silu_c;
+                f32x2 e = {__builtin_amdgcn_exp2f(t.x), __builtin_amdgcn_exp2f(t.y)};
                 e = e + 1.0f;
-                const f2_t rc = {__builtin_amdgcn_rcpf(e.x), __builtin_amdgcn_rcpf(e.y)};
+                const f32x2 rc = {__builtin_amdgcn_rcpf(e.x), __builtin_amdgcn_rcpf(e.y)};
                 v = v * rc;
             }
-            split_pair_scaled(v.x, v.y, ph, pl, am);
+            pair_split_amax(v.x, v.y, ph, pl, am);
         } else {
-            split_pair<false>(xr[i][2 * q], xr[i][2 * q + 1], xs, ph, pl, am);
+            pair_split_scale<false>(xr[i][2 * q], xr[i][2 * q + 1], xs, ph, pl, am);
         }
         st_hi[i][2 * q] = ph.x; st_hi[i][2 * q + 1] = ph.y;
         st_lo[i][2 * q] = pl.x; st_lo[i][2 * q + 1] = pl.y;
@@ -613,6 +608,7 @@ __global__ __launch_bounds__(C::NT, C::NT / 256) void conv_f16x2_pipe_kernel(Con
                 __builtin_amdgcn_sched_barrier(0);
                 continue;
             }
+            // (not f16x2_mma: each term runs over all the tiles before the next -- that order of accumulation is the result)
             if (LC_F16X2_TERMS & 2) {
 #pragma unroll
                 for (int i = 0; i < C::TCO_; ++i)
@@ -1034,10 +1030,10 @@ __device__ __forceinline__ void pack_weight_elems(const float* __restrict__ w, _
         if (co < Co && ci < Ci)
             v = (DX ? w[((long long)ci * Co + co) * ntap + (ntap - 1 - tap)]
                     : w[((long long)co * Ci + ci) * ntap + tap]) * ws;
-        // the split rule of the activations: hi = 11 significant bits (truncated, exact), lo = rest
-        const float hf = __uint_as_float(__float_as_uint(v) & 0xFFFFE000u);
-        ph[e] = (_Float16)hf;
-        pl[e] = (_Float16)(v - hf);
+        _Float16 hf, lf;
+        f16x2_split_scalar(v, hf, lf);      // the split rule of the activations
+        ph[e] = hf;
+        pl[e] = lf;
     }
 }
 

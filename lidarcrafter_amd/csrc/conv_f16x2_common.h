@@ -1,5 +1,6 @@
 // Shared pieces of the f16x2 convolution kernels (conv_f16x2.hip, conv_f16x2_tall.hip): argument block, tile
-// configuration, THE split rule, fused-GroupNorm row derivation, LDS-DMA and wait helpers, the deferred epilogue.
+// configuration, fused-GroupNorm row derivation, LDS-DMA and wait helpers, the deferred epilogue.
+// The operand split, its range publish and the MFMA row map: f16x2.h.
 // The GroupNorm statistics entries the epilogues write and the prologues fold: stats_entry.h.
 // See the header comment of conv_f16x2.hip for the arithmetic.
 #pragma once
@@ -7,6 +8,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "f16x2.h"
 #include "stats_entry.h"
 
 #ifndef LC_EPI_MODE
@@ -28,8 +30,6 @@ __device__ __forceinline__ void epi_store(float* p, float v) {
 #endif
 }
 
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 
 #ifndef LC_ABLATE
 #define LC_ABLATE 0   // developer ablation switches (devtools/ablate_conv.sh); 0 in the product
@@ -59,13 +59,6 @@ typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 #endif
 #ifndef LC_PS_SCHED
 #define LC_PS_SCHED 0   // pre-split kernel: 0 = fence per tap (reads of tap t+1, then MFMAs of tap t), 1 = 1:1 interleave
-#endif
-#ifndef LC_F16X2_TERMS
-// which of the three products are accumulated: bit 0 wh*xh, bit 1 wl*xh, bit 2 wh*xl.  7 in the
-// product library; 3 / 5 exist only to MEASURE what fewer passes cost in accuracy
-// (devtools/passes_error.py, profiles/r02_passes_error.json); 1 = the single-product build
-// liblidarcrafter_hip_p1.so that serves callers running under fp16 autocast (ops.conv_products).
-#define LC_F16X2_TERMS 7
 #endif
 constexpr float X_PRESCALE_DEFAULT = 16.0f, W_PRESCALE_DEFAULT = 256.0f;
 
@@ -213,67 +206,6 @@ struct HCfg {
     static_assert(WCO * WPX == 4 || WCO * WPX == 8, "4 or 8 waves");
 };
 
-// THE split rule of both kernels.  s = v * xs;  hi = s truncated to 11 significant bits (exact in
-// fp32) and packed round-toward-zero -- exact below 65504, saturating (never inf) above;
-// lo = fp16(s - hi) (RTNE; subnormal below 2^-14, zero below 2^-25).  `am` accumulates max |s|.
-typedef _Float16 h2_t __attribute__((ext_vector_type(2)));
-typedef float f2_t __attribute__((ext_vector_type(2)));
-#ifndef LC_SPLIT_ABL
-#define LC_SPLIT_ABL 0   // developer ablation: 1 no amax accumulation, 2 round-to-nearest split
-#endif
-template <bool NOPACK>
-__device__ __forceinline__ void split_pair(float v0, float v1, float xs, h2_t& ph, h2_t& pl, float& am) {
-    float s0 = v0 * xs, s1 = v1 * xs;
-    // NOPACK: keep hipcc's SLP vectoriser from fusing the two multiplies into v_pk_mul_f32 -- the
-    // packed form needs an aligned register pair, and in the 2-blocks/CU kernel the v_mov_b64 that
-    // builds it (with its s_waitcnt) lands between the global loads of the next chunk and
-    // serialises them (1x1 convs 26 -> 35 us, 33 -> 61 us, measured r02g)
-    if (NOPACK) asm volatile("" : "+v"(s0), "+v"(s1));
-    if (!(LC_SPLIT_ABL & 1))
-        am = __builtin_fmaxf(am, __builtin_fmaxf(__builtin_fabsf(s0), __builtin_fabsf(s1)));   // v_max3_f32
-    if (LC_SPLIT_ABL & 2) {
-        const _Float16 a0 = (_Float16)s0, a1 = (_Float16)s1;
-        ph.x = a0; ph.y = a1;
-        pl.x = (_Float16)(s0 - (float)a0); pl.y = (_Float16)(s1 - (float)a1);
-        return;
-    }
-    const float h0 = __uint_as_float(__float_as_uint(s0) & 0xFFFFE000u);
-    const float h1 = __uint_as_float(__float_as_uint(s1) & 0xFFFFE000u);
-    ph = __builtin_bit_cast(h2_t, __builtin_amdgcn_cvt_pkrtz(h0, h1));
-    f2_t r; r.x = s0 - h0; r.y = s1 - h1;
-    pl = __builtin_convertvector(r, h2_t);
-}
-// the same rule for values that already carry the scale (fused GroupNorm rows are pre-multiplied)
-__device__ __forceinline__ void split_pair_scaled(float s0, float s1, h2_t& ph, h2_t& pl, float& am) {
-    am = __builtin_fmaxf(am, __builtin_fmaxf(__builtin_fabsf(s0), __builtin_fabsf(s1)));       // v_max3_f32
-    const float h0 = __uint_as_float(__float_as_uint(s0) & 0xFFFFE000u);
-    const float h1 = __uint_as_float(__float_as_uint(s1) & 0xFFFFE000u);
-    ph = __builtin_bit_cast(h2_t, __builtin_amdgcn_cvt_pkrtz(h0, h1));
-    f2_t r; r.x = s0 - h0; r.y = s1 - h1;
-    pl = __builtin_convertvector(r, h2_t);
-}
-template <bool NOPACK = false>
-__device__ __forceinline__ void split8(const float (&v)[8], float xs, half8& hi, half8& lo, float& am) {
-#pragma unroll
-    for (int k = 0; k < 8; k += 2) {
-        h2_t ph, pl;
-        split_pair<NOPACK>(v[k], v[k + 1], xs, ph, pl, am);
-        hi[k] = ph.x; hi[k + 1] = ph.y; lo[k] = pl.x; lo[k + 1] = pl.y;
-    }
-}
-// publish the wave's max |x * x_scale| (am >= 0: unsigned order == float order); a cached read
-// keeps all but the first few blocks of a launch off the atomic
-#ifndef LC_RANGE_ABL
-#define LC_RANGE_ABL 0   // developer ablation: 1 no amax publish, 2 constant scales (no device loads)
-#endif
-__device__ __forceinline__ void publish_amax(lc_conv_range* rg, float am, float seen) {
-    if (LC_RANGE_ABL & 1) return;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) am = __builtin_fmaxf(am, __shfl_xor(am, o, 64));
-    if ((threadIdx.x & 63) == 0 && am > seen)
-        atomicMax(reinterpret_cast<unsigned*>(&rg->amax_scaled), __float_as_uint(am));
-}
-
 typedef __attribute__((address_space(3))) void* lds_vptr;
 typedef const __attribute__((address_space(1))) void* gbl_vptr;
 
@@ -397,8 +329,9 @@ struct DefEpi {                // branch here split the MFMAs' basic block -- le
     static __device__ __forceinline__ int i_of(int k) { return k / (16 * TPX); }
     static __device__ __forceinline__ int m_of(int k) { return (k / OCTV) & 3; }
     static __device__ __forceinline__ int j_of(int k) { return (k >> 2) % TPX; }
-    static __device__ __forceinline__ int cor_of(int k) {   // channel of value k relative to co_wave
-        return i_of(k) * 32 + (k & 3) + 8 * m_of(k);
+    static __device__ __forceinline__ int cor_of(int k) {   // channel of value k relative to co_wave: mfma_row (f16x2.h) of
+        return i_of(k) * 32 + (k & 3) + 8 * m_of(k);        // register r = 4 m + (k & 3), written in m (through mfma_row the
+                                                            // three spilling instantiations commute a few operands)
     }
     __device__ __forceinline__ unsigned off_of(int k) const {
         return (co_wave + cor_of(k) < Co) ? voff[j_of(k)] : OOB;

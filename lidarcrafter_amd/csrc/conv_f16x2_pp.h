@@ -136,12 +136,11 @@ __global__ __launch_bounds__(512, 1) void conv_f16x2_pp_kernel(ConvArgsH a) {
     };
     auto load_x = [&](XSet& xs_, int v) __attribute__((always_inline)) {   // (past the last step: a valid chunk, never staged)
         if (LC_PP_ABL & 2) return;
-        typedef unsigned u2_t __attribute__((ext_vector_type(2)));
         const int ch = v % nchunk;
         xs_.voff = x_offset(v);
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
-            const u2_t d = __builtin_amdgcn_raw_buffer_load_b64(rs_x, xs_.voff, (unsigned)(ch * 16 + k) * HW * 4u, 0);
+            const u32x2 d = __builtin_amdgcn_raw_buffer_load_b64(rs_x, xs_.voff, (unsigned)(ch * 16 + k) * HW * 4u, 0);
             xs_.v[0][k] = __uint_as_float(d.x);
             xs_.v[1][k] = __uint_as_float(d.y);
         }
@@ -206,23 +205,23 @@ __global__ __launch_bounds__(512, 1) void conv_f16x2_pp_kernel(ConvArgsH a) {
         half8 hi, lo;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            h2_t ph, pl;
+            half2v ph, pl;
             if constexpr (GNM != 0) {
                 const f32x4* g = xs_.voff != 0xFFFFFFF0u ? ctab + ch * 8 + grp * 4 : ctab + (a.Cgn >> 1);
                 const f32x4 row = g[q];
-                f2_t v = {xs_.v[i][2 * q], xs_.v[i][2 * q + 1]};
-                const f2_t A = {row.x, row.y}, Bv = {row.z, row.w};
+                f32x2 v = {xs_.v[i][2 * q], xs_.v[i][2 * q + 1]};
+                const f32x2 A = {row.x, row.y}, Bv = {row.z, row.w};
                 v = __builtin_elementwise_fma(v, A, Bv);
                 if constexpr (GNM == 1) {
-                    const f2_t t = v * silu_c;
-                    f2_t e = {__builtin_amdgcn_exp2f(t.x), __builtin_amdgcn_exp2f(t.y)};
+                    const f32x2 t = v * silu_c;
+                    f32x2 e = {__builtin_amdgcn_exp2f(t.x), __builtin_amdgcn_exp2f(t.y)};
                     e = e + 1.0f;
-                    const f2_t rc = {__builtin_amdgcn_rcpf(e.x), __builtin_amdgcn_rcpf(e.y)};
+                    const f32x2 rc = {__builtin_amdgcn_rcpf(e.x), __builtin_amdgcn_rcpf(e.y)};
                     v = v * rc;
                 }
-                split_pair_scaled(v.x, v.y, ph, pl, am);
+                pair_split_amax(v.x, v.y, ph, pl, am);
             } else {
-                split_pair<false>(xs_.v[i][2 * q], xs_.v[i][2 * q + 1], xs, ph, pl, am);
+                pair_split_scale<false>(xs_.v[i][2 * q], xs_.v[i][2 * q + 1], xs, ph, pl, am);
             }
             hi[2 * q] = ph.x; hi[2 * q + 1] = ph.y;
             lo[2 * q] = pl.x; lo[2 * q + 1] = pl.y;
@@ -403,9 +402,7 @@ __global__ __launch_bounds__(512, 1) void conv_f16x2_pp_kernel(ConvArgsH a) {
             }
 #pragma unroll
             for (int j = 0; j < TPX; ++j) {
-                if (LC_F16X2_TERMS & 2) acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[s], bh[s][j], acc[j], 0, 0, 0);
-                if (LC_F16X2_TERMS & 4) acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[s], bl[s][j], acc[j], 0, 0, 0);
-                acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[s], bh[s][j], acc[j], 0, 0, 0);
+                acc[j] = f16x2_mma<LC_F16X2_TERMS>(acc[j], ah[s], al[s], bh[s][j], bl[s][j]);   // back to back per accumulator
             }
         }
         __builtin_amdgcn_sched_barrier(0);

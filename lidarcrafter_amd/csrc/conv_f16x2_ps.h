@@ -208,6 +208,7 @@ __global__ __launch_bounds__(C::NT, C::NT / 256) void conv_f16x2_ps_kernel(ConvA
             for (int q = 0; q < SPT; ++q)
                 if (tap * SPT + q < IPW) issue_slot(nxt, tap * SPT + q, xso, wso);
             if (LC_PS_SCHED == 0) __builtin_amdgcn_sched_barrier(0);
+            // (not f16x2_mma: each term runs over all the tiles before the next -- that order of accumulation is the result)
             if (LC_F16X2_TERMS & 2) {
 #pragma unroll
                 for (int i = 0; i < C::TCO_; ++i)
@@ -253,7 +254,7 @@ __global__ __launch_bounds__(C::NT, C::NT / 256) void conv_f16x2_ps_kernel(ConvA
     for (int i = 0; i < C::TCO_; ++i)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int co = co_wave + i * 32 + (r & 3) + 8 * (r >> 2);
+            const int co = co_wave + i * 32 + mfma_row(r);
             bias_r[i][r] = (a.bias && co < a.Co) ? a.bias[co] : 0.0f;
         }
     float res_r[C::TCO_][C::TPX_][16];
@@ -281,7 +282,7 @@ __global__ __launch_bounds__(C::NT, C::NT / 256) void conv_f16x2_ps_kernel(ConvA
             for (int i = 0; i < C::TCO_; ++i)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int cor = i * 32 + (r & 3) + 8 * (r >> 2);
+                    const int cor = i * 32 + mfma_row(r);
                     res_r[i][j][r] = (LC_PS_ABL & 16) ? 0.0f : __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
                         rs_rb, co_wave + cor < a.Co ? vo : OOB, (unsigned)cor * HW4, 0));
                 }
@@ -315,7 +316,7 @@ __global__ __launch_bounds__(C::NT, C::NT / 256) void conv_f16x2_ps_kernel(ConvA
                 for (int i = 0; i < C::TCO_; ++i)
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
-                        const int co = co_wave + i * 32 + (r & 3) + 8 * (r >> 2);
+                        const int co = co_wave + i * 32 + mfma_row(r);
                         if (pok && co < a.Co) epi_store(&pb[(long long)co * HW + poff], acc[i][j][r] * out_unscale);
                         acc[i][j][r] = 0.0f;
                     }
@@ -340,7 +341,7 @@ __global__ __launch_bounds__(C::NT, C::NT / 256) void conv_f16x2_ps_kernel(ConvA
             for (int i = 0; i < C::TCO_; ++i) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int co = co_wave + i * 32 + (r & 3) + 8 * (r >> 2);
+                    const int co = co_wave + i * 32 + mfma_row(r);
                     // (S2: the FIR behind the conv zero-pads the conv's OUTPUT, so the bias reaches the image's first / last
                     //  row through three of the four vertical taps only: 1 - f0 = 1 - f3 = 7/8)
                     float bia = bias_r[i][r];
@@ -349,7 +350,7 @@ __global__ __launch_bounds__(C::NT, C::NT / 256) void conv_f16x2_ps_kernel(ConvA
                                     a.out_scale;
                     if (!(LC_PS_ABL & 16))
                         __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rs_yb, co < a.Co ? vo_j : OOB,
-                                                              (unsigned)(i * 32 + (r & 3) + 8 * (r >> 2)) * HW4, LC_DEF_AUX);
+                                                              (unsigned)(i * 32 + mfma_row(r)) * HW4, LC_DEF_AUX);
                     if constexpr (EMIT_STATS && !(LC_EMIT_ABL & 1)) {
                         const int m = r >> 2;
                         if (j == 0 && (r & 3) == 0) st[i][m].start(pok ? v : 0.0f, upper_quad);

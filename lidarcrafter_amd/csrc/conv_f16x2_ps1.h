@@ -17,6 +17,8 @@
 #pragma once
 #include <type_traits>
 
+#include "attention_split.h"      // QK_PRE
+
 namespace {
 
 // BPV = pixels per block: 256 (8 waves, 2 x 48 KB of LDS: one block per CU) or 128 (4 waves, 2 x 32 KB: two blocks per CU --
@@ -60,16 +62,12 @@ struct P1Args {
 };
 
 // The 8-byte halves of a K unit / the 16-byte V units a lane of the QKV epilogue owns; the split is the attention kernels'
-// own (attention_split.h: pre-scale 16, hi = 11 leading bits, lo = fp16(rest)).
+// own (f16x2.h, pre-scale QK_PRE of attention_split.h).
 __device__ __forceinline__ void qkv_split2(float a, float b, unsigned& hi, unsigned& lo) {
-    typedef float f2 __attribute__((ext_vector_type(2)));
-    typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-    const float s0 = a * 16.0f, s1 = b * 16.0f;
-    const float h0 = __uint_as_float(__float_as_uint(s0) & 0xFFFFE000u);
-    const float h1 = __uint_as_float(__float_as_uint(s1) & 0xFFFFE000u);
-    hi = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(h0, h1));
-    f2 r; r.x = s0 - h0; r.y = s1 - h1;
-    lo = __builtin_bit_cast(unsigned, __builtin_convertvector(r, h2));
+    half2v ph, pl;
+    pair_split(a * QK_PRE, b * QK_PRE, ph, pl);
+    hi = __builtin_bit_cast(unsigned, ph);
+    lo = __builtin_bit_cast(unsigned, pl);
 }
 
 template <bool QKV, int BPV = 256, int BNV = 128, int MIV = 2>
@@ -183,14 +181,12 @@ __global__ __launch_bounds__((P1T<BPV, BNV, MIV>::NT), (BPV == 256 || BNV != 128
                 for (int i = 0; i < MI; ++i)
 #pragma unroll
                     for (int j = 0; j < 2; ++j) {
-                        if (VT) {
+                        if (VT) {      // (not f16x2_mma: operands swapped, ah * bl first)
                             if (LC_F16X2_TERMS & 2) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh[j], al[i], acc[i][j], 0, 0, 0);
                             if (LC_F16X2_TERMS & 4) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bl[j], ah[i], acc[i][j], 0, 0, 0);
                             acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh[j], ah[i], acc[i][j], 0, 0, 0);
                         } else {
-                            if (LC_F16X2_TERMS & 2) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[i], bh[j], acc[i][j], 0, 0, 0);
-                            if (LC_F16X2_TERMS & 4) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bl[j], acc[i][j], 0, 0, 0);
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bh[j], acc[i][j], 0, 0, 0);
+                            acc[i][j] = f16x2_mma<LC_F16X2_TERMS>(acc[i][j], ah[i], al[i], bh[j], bl[j]);
                         }
                     }
             }
@@ -212,7 +208,7 @@ __global__ __launch_bounds__((P1T<BPV, BNV, MIV>::NT), (BPV == 256 || BNV != 128
     for (int i = 0; i < MI; ++i)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int co = co_lane + i * 32 + (r & 3) + 8 * (r >> 2);
+            const int co = co_lane + i * 32 + mfma_row(r);
             // (QKV value blocks: the accumulators are transposed, a lane owns ONE channel per 32-block)
             const int cb_ = (QKV && vt) ? co0 + wco * WCO + i * 32 + l31 : co;
             bias_r[i][r] = (a.bias && cb_ < a.Co) ? a.bias[cb_] : 0.0f;
@@ -280,7 +276,7 @@ __global__ __launch_bounds__((P1T<BPV, BNV, MIV>::NT), (BPV == 256 || BNV != 128
                 __builtin_amdgcn_wave_barrier();
 #pragma unroll
                 for (int r = 0; r < 16; ++r)
-                    strip[((r & 3) + 8 * (r >> 2) + 4 * kh) * 36 + l31] = (acc[i][j][r] * out_unscale + bias_r[i][r]) * a.out_scale;
+                    strip[mfma_row(r, kh) * 36 + l31] = (acc[i][j][r] * out_unscale + bias_r[i][r]) * a.out_scale;
                 __builtin_amdgcn_wave_barrier();
                 const int cob = co0 + wco * WCO + i * 32, pb_ = p0 + wpx * 64 + j * 32 + 4 * (lane & 7);
                 // (all four reads first, into four register quads: no instruction may write the data registers of a
@@ -307,14 +303,14 @@ __global__ __launch_bounds__((P1T<BPV, BNV, MIV>::NT), (BPV == 256 || BNV != 128
         for (int i = 0; i < MI; ++i)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int co = co_lane + i * 32 + (r & 3) + 8 * (r >> 2);
+                const int co = co_lane + i * 32 + mfma_row(r);
                 res_r[i][r] = (rb && pok && co < a.Co) ? rb[(long long)co * a.P + p] : 0.0f;
             }
 #pragma unroll
         for (int i = 0; i < MI; ++i)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int co = co_lane + i * 32 + (r & 3) + 8 * (r >> 2);
+                const int co = co_lane + i * 32 + mfma_row(r);
                 if (pok && co < a.Co)
                     epi_store(&yb[(long long)co * a.P + p],
                               ((acc[i][j][r] * out_unscale + bias_r[i][r]) + res_r[i][r]) * a.out_scale);

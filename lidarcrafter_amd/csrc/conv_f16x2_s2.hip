@@ -30,14 +30,12 @@ namespace {
 
 #include "conv_f16x2_ps.h"
 
-typedef _Float16 half8_s2 __attribute__((ext_vector_type(8)));
-
 // thread = (channel octet, column pair (2 i, 2 i + 1), row strip); it walks its strip of F rows with a sliding window of four
 // W-filtered rows (8 channels x 2 columns each) in registers, so x is read once (plus 3 halo rows per strip).  The raw
 // values of the NEXT input row are requested before the current row's filter / split / stores (the walk is a serial chain of
 // HBM round trips otherwise: first version 42.6 us for 67 MB in + 69 MB out at 8 x 64 x 32 x 1024, profiles/r06_fold_down.txt).
 __global__ __launch_bounds__(256) void fir_down2_prefilter_split_kernel(
-    const float* __restrict__ x, long long x_bs, half8_s2* __restrict__ ysp, int C8, int H, int W, int nstrip, int strip_len,
+    const float* __restrict__ x, long long x_bs, half8* __restrict__ ysp, int C8, int H, int W, int nstrip, int strip_len,
     lc_conv_range* range) {
     const int Wh = W >> 1;
     const int i = blockIdx.x * 256 + threadIdx.x;            // column pair
@@ -49,8 +47,8 @@ __global__ __launch_bounds__(256) void fir_down2_prefilter_split_kernel(
         const long long HW = (long long)H * W;
         const float* xb = x + b * x_bs + (long long)c8 * 8 * HW;
         const int R = H + 3;
-        half8_s2* yh = ysp + ((long long)b * 2 * C8 + c8) * R * W;          // hi plane of this octet: rows of W units
-        half8_s2* yl = yh + (long long)C8 * R * W;
+        half8* yh = ysp + ((long long)b * 2 * C8 + c8) * R * W;          // hi plane of this octet: rows of W units
+        half8* yl = yh + (long long)C8 * R * W;
         const int cm1 = (2 * i - 1 + W) % W, cp2 = (2 * i + 2) % W;         // (cp2 is even: columns cp2, cp2 + 1 are one float2)
         constexpr float f0 = 0.125f, f1 = 0.375f, f2 = 0.375f, f3 = 0.125f;
         struct Raw { float a[8]; float2 m[8], c[8]; };
@@ -268,9 +266,7 @@ __global__ __launch_bounds__(256, 1) void conv_s2_shared_w_kernel(ConvArgsH a) {
                 }
             }
             __builtin_amdgcn_sched_barrier(0);
-            if (LC_F16X2_TERMS & 2) acc[T] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[s], bh[s], acc[T], 0, 0, 0);
-            if (LC_F16X2_TERMS & 4) acc[T] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[s], bl[s], acc[T], 0, 0, 0);
-            acc[T] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[s], bh[s], acc[T], 0, 0, 0);
+            acc[T] = f16x2_mma<LC_F16X2_TERMS>(acc[T], ah[s], al[s], bh[s], bl[s]);   // back to back per accumulator
         }
         __builtin_amdgcn_sched_barrier(0);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -286,7 +282,7 @@ __global__ __launch_bounds__(256, 1) void conv_s2_shared_w_kernel(ConvArgsH a) {
     float bias_r[16];
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        const int co = co_wave + (r & 3) + 8 * (r >> 2);
+        const int co = co_wave + mfma_row(r);
         bias_r[r] = (a.bias && co < a.Co) ? a.bias[co] : 0.0f;
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -335,7 +331,7 @@ __global__ __launch_bounds__(256, 1) void conv_s2_shared_w_kernel(ConvArgsH a) {
         const bool upper_quad = quads && (lane & 32);
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int cor = (r & 3) + 8 * (r >> 2);
+            const int cor = mfma_row(r);
             const float v = (acc[t][r] * out_unscale + bias_r[r] * brow) * a.out_scale;
             __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rs_yb, co_wave + cor < a.Co ? vo : OOB,
                                                   (unsigned)cor * HW4, LC_DEF_AUX);
@@ -386,7 +382,7 @@ extern "C" int lc_fir_down2_prefilter_split(const float* x, int64_t x_bs, void* 
     if ((long long)B * nstrip > 65535) return LC_EUNSUP;
     dim3 grid((W / 2 + 255) / 256, C / 8, B * nstrip);
     hipLaunchKernelGGL(fir_down2_prefilter_split_kernel, grid, dim3(256), 0, lc_s(s), x, (long long)x_bs,
-                       reinterpret_cast<half8_s2*>(y_split), C / 8, H, W, nstrip, strip_len, range);
+                       reinterpret_cast<half8*>(y_split), C / 8, H, W, nstrip, strip_len, range);
     return lc_launch_status();
 }
 

@@ -86,9 +86,6 @@ extern "C" int lc_debug_read_tall(unsigned long long* out32, int reset) {
 
 namespace {
 
-typedef _Float16 h4_t __attribute__((ext_vector_type(4)));
-typedef unsigned u2_t __attribute__((ext_vector_type(2)));
-
 struct TLG {   // geometry
     static constexpr int TH = 4, TW = 64, BN = 64, CB = 2, NTAP = 9, NT = 512;
     static constexpr int RS = 66, CBS = 2 * RS, PLS = CB * CBS, RPU = 2 * PLS;      // row, channel block, plane, region (units)
@@ -165,12 +162,12 @@ __global__ __launch_bounds__(512, 2) void conv_f16x2_tall_kernel(ConvArgsH a) {
         xe_voff = xe_ok ? (unsigned)((scb * 8 + shalf * 4 + e_chq) * HW + ghe * W + gwe) * 4u : XOOB;
     };
     // a loaded chunk: 4 channels x 2 pixels + one edge element, with the in-image flags of the tile it belongs to
-    struct XSet { u2_t m[4]; float e; bool ok_m, ok_e; };
+    struct XSet { u32x2 m[4]; float e; bool ok_m, ok_e; };
     XSet xset[2];
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
 #pragma unroll
-        for (int k = 0; k < 4; ++k) xset[i].m[k] = u2_t{0u, 0u};
+        for (int k = 0; k < 4; ++k) xset[i].m[k] = u32x2{0u, 0u};
         xset[i].e = 0.f; xset[i].ok_m = xset[i].ok_e = false;
     }
     auto load_x = [&](XSet& xv, int ch) __attribute__((always_inline)) {
@@ -185,22 +182,22 @@ __global__ __launch_bounds__(512, 2) void conv_f16x2_tall_kernel(ConvArgsH a) {
     const int dm_lane = (scb * CBS + rsub * RS + 1 + 2 * pair) * 16 + shalf * 8;
     const int de_lane = (scb * CBS + e_rsub * RS + (e_side ? RS - 1 : 0)) * 16 + (shalf * 4 + e_chq) * 2;
 
-    auto stage_pair2 = [&](float x0, float x1, const f32x4 row, h2_t& ph, h2_t& pl) __attribute__((always_inline)) {
-        if (LC_TALL_ABL & 2) { ph = h2_t{0, 0}; pl = h2_t{0, 0}; asm volatile("" ::"v"(x0), "v"(x1)); return; }
+    auto stage_pair2 = [&](float x0, float x1, const f32x4 row, half2v& ph, half2v& pl) __attribute__((always_inline)) {
+        if (LC_TALL_ABL & 2) { ph = half2v{0, 0}; pl = half2v{0, 0}; asm volatile("" ::"v"(x0), "v"(x1)); return; }
         if constexpr (GNM != 0) {
-            f2_t v = {x0, x1};
-            const f2_t A = {row.x, row.y}, Bv = {row.z, row.w};
+            f32x2 v = {x0, x1};
+            const f32x2 A = {row.x, row.y}, Bv = {row.z, row.w};
             v = __builtin_elementwise_fma(v, A, Bv);
             if constexpr (GNM == 1) {
-                const f2_t t = v * silu_c;
-                f2_t e = {__builtin_amdgcn_exp2f(t.x), __builtin_amdgcn_exp2f(t.y)};
+                const f32x2 t = v * silu_c;
+                f32x2 e = {__builtin_amdgcn_exp2f(t.x), __builtin_amdgcn_exp2f(t.y)};
                 e = e + 1.0f;
-                const f2_t rc = {__builtin_amdgcn_rcpf(e.x), __builtin_amdgcn_rcpf(e.y)};
+                const f32x2 rc = {__builtin_amdgcn_rcpf(e.x), __builtin_amdgcn_rcpf(e.y)};
                 v = v * rc;
             }
-            split_pair_scaled(v.x, v.y, ph, pl, am);
+            pair_split_amax(v.x, v.y, ph, pl, am);
         } else {
-            split_pair<false>(x0, x1, xs, ph, pl, am);
+            pair_split_scale<false>(x0, x1, xs, ph, pl, am);
         }
     };
     // fused-GroupNorm rows of the main task (pair quads (A0, A1, B0, B1) x xs; 4 zero quads behind the table)
@@ -216,16 +213,16 @@ __global__ __launch_bounds__(512, 2) void conv_f16x2_tall_kernel(ConvArgsH a) {
     auto stage_px = [&](const XSet& xv, int p, int dreg_b) __attribute__((always_inline)) {   // pixel p of the pair -> region at byte dreg_b
         const float v0 = __uint_as_float(xv.m[0][p]), v1 = __uint_as_float(xv.m[1][p]);
         const float v2 = __uint_as_float(xv.m[2][p]), v3 = __uint_as_float(xv.m[3][p]);
-        h2_t h0, l0, h1, l1;
+        half2v h0, l0, h1, l1;
         stage_pair2(v0, v1, grow[0], h0, l0);
         stage_pair2(v2, v3, grow[1], h1, l1);
-        const h4_t hv = {h0.x, h0.y, h1.x, h1.y}, lv = {l0.x, l0.y, l1.x, l1.y};
+        const half4 hv = {h0.x, h0.y, h1.x, h1.y}, lv = {l0.x, l0.y, l1.x, l1.y};
         char* d = ldsb + dreg_b + dm_lane + p * 16;
-        *reinterpret_cast<h4_t*>(d) = hv;
-        *reinterpret_cast<h4_t*>(d + PLS * 16) = lv;
+        *reinterpret_cast<half4*>(d) = hv;
+        *reinterpret_cast<half4*>(d + PLS * 16) = lv;
     };
     auto stage_edge = [&](const XSet& xv, int ch, int dreg_b) __attribute__((always_inline)) {   // lanes 0..15: one halo-column element each
-        h2_t ph, pl;
+        half2v ph, pl;
         if constexpr (GNM != 0) {
             const float* cf = reinterpret_cast<const float*>(ctab);
             const int qi = xv.ok_e ? (ch * 8 + scb * 4 + shalf * 2 + (e_chq >> 1)) * 4 + (e_chq & 1) : (a.Cgn >> 1) * 4;
@@ -286,7 +283,7 @@ __global__ __launch_bounds__(512, 2) void conv_f16x2_tall_kernel(ConvArgsH a) {
     if (AH == 2) load_x(xset[1], 1);
     // ... and the loads of the block's top rows (staged behind the GroupNorm fold below): NTR rounds of 4 x 64 bits
     constexpr int NTOP = NCH * 2 * 2 * 2 * 34, NTR = (NTOP + G::NT - 1) / G::NT;
-    u2_t tv[NTR][4];
+    u32x2 tv[NTR][4];
 #pragma unroll
     for (int rd = 0; rd < NTR; ++rd) {
         const int t = tid + rd * G::NT;
@@ -346,13 +343,13 @@ __global__ __launch_bounds__(512, 2) void conv_f16x2_tall_kernel(ConvArgsH a) {
 #pragma unroll
             for (int e = 0; e < 2; ++e) {
                 const int uc = 2 * pp - 1 + e;
-                h2_t h0, l0, h1, l1;
+                half2v h0, l0, h1, l1;
                 stage_pair2(__uint_as_float(tv[rd][0][e]), __uint_as_float(tv[rd][1][e]), r0, h0, l0);
                 stage_pair2(__uint_as_float(tv[rd][2][e]), __uint_as_float(tv[rd][3][e]), r1, h1, l1);
                 if (uc >= 0 && uc < RS) {
                     char* d = ldsb + ((G::KEEP0 + c * RPU + cb * CBS + row * RS + uc) * 16 + hf * 8);
-                    *reinterpret_cast<h4_t*>(d) = h4_t{h0.x, h0.y, h1.x, h1.y};
-                    *reinterpret_cast<h4_t*>(d + PLS * 16) = h4_t{l0.x, l0.y, l1.x, l1.y};
+                    *reinterpret_cast<half4*>(d) = half4{h0.x, h0.y, h1.x, h1.y};
+                    *reinterpret_cast<half4*>(d + PLS * 16) = half4{l0.x, l0.y, l1.x, l1.y};
                 }
             }
         }
@@ -462,6 +459,7 @@ __global__ __launch_bounds__(512, 2) void conv_f16x2_tall_kernel(ConvArgsH a) {
                 __builtin_amdgcn_sched_barrier(0);
                 continue;
             }
+            // (not f16x2_mma: each term runs over all the tiles before the next -- that order of accumulation is the result)
             if (LC_F16X2_TERMS & 2) {
 #pragma unroll
                 for (int j = 0; j < 2; ++j) acc[0][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl_[s], xh_[s][j], acc[0][j], 0, 0, 0);

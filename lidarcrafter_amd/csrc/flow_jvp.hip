@@ -23,16 +23,7 @@
 namespace {
 
 // ---- GroupNorm ----------------------------------------------------------------------------------------------------------
-// the chunking of norm.hip's statistics pass (gn_chunk_elems / gn_chunks): the first two partials must be formed over the
-// same spans in the same order
-__host__ __device__ inline int gnj_chunk_elems(int B, int G, long long n) {
-    const long long blocks = (long long)B * G * ((n + 16383) / 16384);
-    return blocks >= 512 ? 16384 : 4096;
-}
-__host__ __device__ inline int gnj_chunks(int B, int G, long long n) {
-    const int ce = gnj_chunk_elems(B, G, n);
-    return (int)((n + ce - 1) / ce);
-}
+// (the chunking of the statistics partials: gn_chunk_elems / gn_chunks of common.h, shared with norm.hip)
 // launch shape of norm.hip's apply pass (gn_apply_grid): the partial maxima of |y| come out in the same count and order
 inline void gnj_apply_grid(int B, int C, int G, long long HW, int* slabs, int* cpb) {
     int sl = (int)((HW + 4095) / 4096);
@@ -343,7 +334,7 @@ __global__ __launch_bounds__(256) void attn_jvp_kernel(AttnJvpArgs a) {
 // ---- entry points ---------------------------------------------------------------------------------------------------------
 extern "C" int64_t lc_groupnorm_jvp_partials_elems(int B, int C, int H, int W, int G) {
     if (B <= 0 || G <= 0 || C <= 0 || C % G || H <= 0 || W <= 0) return 0;
-    return (int64_t)B * G * gnj_chunks(B, G, (long long)(C / G) * H * W) * 4;
+    return (int64_t)B * G * gn_chunks(B, G, (long long)(C / G) * H * W) * 4;
 }
 
 extern "C" int lc_groupnorm_jvp_stats(const float* x, int64_t x_bs, const float* dx, int64_t dx_bs, double* partials,
@@ -352,9 +343,9 @@ extern "C" int lc_groupnorm_jvp_stats(const float* x, int64_t x_bs, const float*
     if (B > 65535 || G > 65535) return LC_EUNSUP;
     const long long HW = (long long)H * W;
     const long long n = (long long)(C / G) * HW;
-    const int nch = gnj_chunks(B, G, n);
+    const int nch = gn_chunks(B, G, n);
     hipLaunchKernelGGL(gn_jvp_stats_kernel, dim3(nch, G, B), dim3(256), 0, lc_s(s), x, (long long)x_bs, dx,
-                       (long long)dx_bs, partials, C, G, HW, nch, gnj_chunk_elems(B, G, n));
+                       (long long)dx_bs, partials, C, G, HW, nch, gn_chunk_elems(B, G, n));
     return lc_launch_status();
 }
 
@@ -369,7 +360,7 @@ extern "C" int lc_groupnorm_jvp_apply_train(const float* x, int64_t x_bs, const 
     if ((gamma == nullptr) != (beta == nullptr) || (dscale && !scale) || (dshift && !shift)) return LC_EINVAL;
     if (B > 65535) return LC_EUNSUP;
     const long long HW = (long long)H * W;
-    const int nch = gnj_chunks(B, G, (long long)(C / G) * HW);
+    const int nch = gn_chunks(B, G, (long long)(C / G) * HW);
     int slabs, cpb;
     gnj_apply_grid(B, C, G, HW, &slabs, &cpb);
     hipLaunchKernelGGL(gn_jvp_apply_kernel, dim3(slabs, C / cpb, B), dim3(256), 0, lc_s(s), x, (long long)x_bs, dx,

@@ -67,8 +67,6 @@ __global__ __launch_bounds__(256) void rmsnorm_kernel(const float* __restrict__ 
     }
 }
 
-__device__ __forceinline__ float gelu_erf(float g) { return 0.5f * g * (1.0f + erff(g * 0.70710678118654752f)); }
-
 __global__ __launch_bounds__(256) void geglu_kernel(const float* __restrict__ x, long long x_bs, float* y,
                                                     long long y_bs, int mid, int L) {
     const int b = blockIdx.y;

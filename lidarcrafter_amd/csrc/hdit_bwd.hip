@@ -111,8 +111,6 @@ __global__ __launch_bounds__(256) void rmsnorm_dparam_kernel(const float* __rest
     if (threadIdx.x == 0) df[(mode == 1 ? blockIdx.y * df_bs : 0) + c] = (float)s;
 }
 
-__device__ __forceinline__ float gelu_erf(float g) { return 0.5f * g * (1.0f + erff(g * 0.70710678118654752f)); }
-
 __device__ __forceinline__ float dgelu_erf(float g) {
     return 0.5f * (1.0f + erff(g * 0.70710678118654752f)) + g * 0.39894228040143268f * expf(-0.5f * g * g);
 }

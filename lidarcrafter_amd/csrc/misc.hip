@@ -1,6 +1,7 @@
 // Small kernels around the denoiser: dense layers of the time/AdaGN MLPs, sinusoid embedding,
 // the fused reverse-diffusion update, strided copy and residual add.  All HBM/latency bound.
 #include "common.h"
+#include "f16x2.h"      // half8
 
 namespace {
 
@@ -158,15 +159,14 @@ __global__ __launch_bounds__(256) void add_scale_kernel(const float* __restrict_
 // A bare v_mfma_f32_32x32x16_f16 loop on operands the CALLER supplies (random fp16: the chip clocks to its power budget,
 // and what a matrix pipe sustains depends on the operand bits -- profiles/r01_e_ubench_mfma.txt: 2.24 PFLOP/s on zeros,
 // 1.69 on random data), 4 independent accumulators per wave, 8 waves per block; and a streaming float4 copy.
-typedef _Float16 cal_half8 __attribute__((ext_vector_type(8)));
-__global__ __launch_bounds__(512) void calib_mfma_kernel(const cal_half8* __restrict__ ops, int iters, float* __restrict__ sink) {
+__global__ __launch_bounds__(512) void calib_mfma_kernel(const half8* __restrict__ ops, int iters, float* __restrict__ sink) {
     f32x16 acc[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
     const int t = blockIdx.x * 512 + threadIdx.x;
-    cal_half8 a[2], b[2];
+    half8 a[2], b[2];
     a[0] = ops[4 * t]; a[1] = ops[4 * t + 1]; b[0] = ops[4 * t + 2]; b[1] = ops[4 * t + 3];
     for (int it = 0; it < iters; ++it) {
 #pragma unroll
@@ -198,7 +198,7 @@ extern "C" int lc_abi_version(void) { return 6; }
 
 extern "C" int64_t lc_calibrate_mfma_f16(const void* operands, int blocks, int iters, float* sink, lc_stream_t s) {
     if (!operands || !sink || blocks <= 0 || iters <= 0) return LC_EINVAL;
-    hipLaunchKernelGGL(calib_mfma_kernel, dim3(blocks), dim3(512), 0, lc_s(s), reinterpret_cast<const cal_half8*>(operands),
+    hipLaunchKernelGGL(calib_mfma_kernel, dim3(blocks), dim3(512), 0, lc_s(s), reinterpret_cast<const half8*>(operands),
                        iters, sink);
     const int rc = lc_launch_status();
     if (rc != LC_OK) return rc < 0 ? rc : -rc;

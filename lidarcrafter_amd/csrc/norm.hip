@@ -4,20 +4,10 @@
 // tensor once (float4, fp32 lane partials over <=64 values, fp64 wave/block reduction),
 // apply reads once and writes once.  A group is a contiguous span of (C/G)*H*W floats in NCHW.
 #include "common.h"
+#include "f16x2.h"
 #include "stats_entry.h"
 
 namespace {
-
-// elements per statistics block: 64 KiB normally, 16 KiB when the tensor is so small that 64 KiB
-// blocks would leave most CUs idle (deep levels at small batch: 128 blocks for [8,512,4,128])
-__host__ __device__ inline int gn_chunk_elems(int B, int G, long long n) {
-    const long long blocks = (long long)B * G * ((n + 16383) / 16384);
-    return blocks >= 512 ? 16384 : 4096;
-}
-__host__ __device__ inline int gn_chunks(int B, int G, long long n) {
-    const int ce = gn_chunk_elems(B, G, n);
-    return (int)((n + ce - 1) / ce);
-}
 
 __global__ __launch_bounds__(256) void gn_stats_kernel(const float* __restrict__ x, long long x_bs,
                                                       double* __restrict__ part, int C, int G,
@@ -202,14 +192,10 @@ __global__ __launch_bounds__(256) void gn_apply_os_kernel(
 // (two-pass partials, OS = false, or the producer's octet statistics, OS = true), but every thread
 // owns ONE pixel of ONE channel octet: 8 channel loads (coalesced across the wave along W), the
 // affine / AdaGN / SiLU arithmetic of gn_apply_kernel, multiplication by the consumer layer's
-// x_scale, the fp16 hi/lo split of conv_f16x2.hip (split rule restated: hi = 11 significant bits
-// truncated, packed toward zero; lo = fp16(s - hi)) and two 16-byte stores into
+// x_scale, the fp16 hi/lo split (f16x2.h) and two 16-byte stores into
 // ysp[b][plane][c/8][h][w][8].  max |y * x_scale| goes to the consumer's lc_conv_range.  The split
 // therefore runs ONCE per element in a memory-bound kernel instead of once per output-channel
 // block inside the conv's K loop.  Needs C % 16 == 0 and whole octets per group.
-typedef _Float16 half8_t __attribute__((ext_vector_type(8)));
-typedef _Float16 half2_t __attribute__((ext_vector_type(2)));
-typedef float float2_t __attribute__((ext_vector_type(2)));
 
 // ---------------------------------------------------------------------------------------------
 // BACKWARD of GroupNorm (+affine) (+AdaGN scale/shift) (+SiLU)  -- training, SURVEY.md section 8f-4.
@@ -360,7 +346,7 @@ template <int OS>
 __global__ __launch_bounds__(256) void gn_apply_split_kernel(
     const float* __restrict__ x, long long x_bs, const double* __restrict__ part, StatSegs os,
     const float* __restrict__ gamma, const float* __restrict__ beta, const float* __restrict__ scale,
-    const float* __restrict__ shift, long long ss_bs, half8_t* __restrict__ ysp, long long ysp_bs,
+    const float* __restrict__ shift, long long ss_bs, half8* __restrict__ ysp, long long ysp_bs,
     int C, int G, long long HW, int nch, float eps, int act, lc_conv_range* range) {
     __shared__ double sh[12];
     const int oct = blockIdx.y, b = blockIdx.z;
@@ -472,20 +458,17 @@ __global__ __launch_bounds__(256) void gn_apply_split_kernel(
     const float seen = range->amax_scaled;
     float am = 0.0f;
     const int C8 = C >> 3;
-    half8_t* yh = ysp + b * ysp_bs + (long long)oct * HW;
-    half8_t* yl = yh + (long long)C8 * HW;
-    auto one = [&](const float (&v)[8], half8_t& h8, half8_t& l8) {
+    half8* yh = ysp + b * ysp_bs + (long long)oct * HW;
+    half8* yl = yh + (long long)C8 * HW;
+    auto one = [&](const float (&v)[8], half8& h8, half8& l8) {
 #pragma unroll
         for (int k = 0; k < 8; k += 2) {
             float t0 = fmaf(v[k] - mu[k], cA[k], cB[k]), t1 = fmaf(v[k + 1] - mu[k + 1], cA[k + 1], cB[k + 1]);
             if (act) { t0 = lc_silu(t0); t1 = lc_silu(t1); }
             const float s0 = t0 * xs, s1 = t1 * xs;
-            am = fmaxf(am, fmaxf(fabsf(s0), fabsf(s1)));
-            const float h0 = __uint_as_float(__float_as_uint(s0) & 0xFFFFE000u);
-            const float h1 = __uint_as_float(__float_as_uint(s1) & 0xFFFFE000u);
-            const half2_t ph = __builtin_bit_cast(half2_t, __builtin_amdgcn_cvt_pkrtz(h0, h1));
-            float2_t r; r.x = s0 - h0; r.y = s1 - h1;
-            const half2_t pl = __builtin_convertvector(r, half2_t);
+            am = pair_amax(am, s0, s1);      // (by value: `am` handed on by reference from inside this lambda reordered the kernel)
+            half2v ph, pl;
+            pair_split(s0, s1, ph, pl);
             h8[k] = ph.x; h8[k + 1] = ph.y; l8[k] = pl.x; l8[k + 1] = pl.y;
         }
     };
@@ -497,7 +480,7 @@ __global__ __launch_bounds__(256) void gn_apply_split_kernel(
             float v[8];
 #pragma unroll
             for (int k = 0; k < 8; ++k) v[k] = pix[k][i];
-            half8_t h8, l8;
+            half8 h8, l8;
             one(v, h8, l8);
             if (p + 256 * i < hi) { yh[p + 256 * i] = h8; yl[p + 256 * i] = l8; }
         }
@@ -509,6 +492,8 @@ __global__ __launch_bounds__(256) void gn_apply_split_kernel(
         load4(pix, p);
         four(pix, p);
     }
+    // (publish_amax of f16x2.h, written out: called, with `am` captured by the lambdas above, the kernel's registers are
+    // allocated differently)
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) am = fmaxf(am, __shfl_xor(am, o, 64));
     if ((threadIdx.x & 63) == 0 && am > seen)
@@ -689,7 +674,7 @@ extern "C" int lc_groupnorm_apply_split(const float* x, int64_t x_bs, const doub
     StatSegs os = STAT_SEGS_NONE;
     hipLaunchKernelGGL(gn_apply_split_kernel<0>, dim3(split_slabs(B, C, HW), C / 8, B), dim3(256), 0,
                        lc_s(s), x, (long long)x_bs, partials, os, gamma, beta, scale, shift,
-                       (long long)ss_bs, reinterpret_cast<half8_t*>(y_split),
+                       (long long)ss_bs, reinterpret_cast<half8*>(y_split),
                        (long long)2 * (C / 8) * HW, C, G, HW, nch, eps, act_silu, range);
     return lc_launch_status();
 }
@@ -712,11 +697,11 @@ extern "C" int lc_groupnorm_apply_os_split(const float* x, int64_t x_bs, const l
     const dim3 grid(split_slabs(B, C, HW), C / 8, B);
     if (cpg % 8 == 0)
         hipLaunchKernelGGL(gn_apply_split_kernel<1>, grid, dim3(256), 0, lc_s(s), x, (long long)x_bs, nullptr, os, gamma,
-                           beta, scale, shift, (long long)ss_bs, reinterpret_cast<half8_t*>(y_split),
+                           beta, scale, shift, (long long)ss_bs, reinterpret_cast<half8*>(y_split),
                            (long long)2 * (C / 8) * HW, C, G, HW, 0, eps, act_silu, range);
     else
         hipLaunchKernelGGL(gn_apply_split_kernel<2>, grid, dim3(256), 0, lc_s(s), x, (long long)x_bs, nullptr, os, gamma,
-                           beta, scale, shift, (long long)ss_bs, reinterpret_cast<half8_t*>(y_split),
+                           beta, scale, shift, (long long)ss_bs, reinterpret_cast<half8*>(y_split),
                            (long long)2 * (C / 8) * HW, C, G, HW, 0, eps, act_silu, range);
     return lc_launch_status();
 }

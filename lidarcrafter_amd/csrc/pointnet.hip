@@ -19,14 +19,12 @@
 // blocks depend on nothing but the cloud, and the maxima are merged in a fixed order without atomics: the same bits for
 // a cloud in every batch and every run.  A point (0,0,0) is a point like any other.
 #include "common.h"
+#include "f16x2.h"      // mfma_row
 
 namespace {
 
 constexpr int PN_T = 128;                     // points per block
 constexpr int PN_C1 = 64, PN_C2 = 128, PN_C3 = 1024;
-
-// C/D of the 32x32 MFMA: register v of lane (h = lane >> 5) holds row (v & 3) + 8 (v >> 2) + 4 h, column lane & 31
-__device__ __forceinline__ int pn_row(int v, int h) { return (v & 3) + 8 * (v >> 2) + 4 * h; }
 
 __global__ __launch_bounds__(256, 2) void pn_trunk_kernel(const float* __restrict__ x, long long x_bs,
                                                       const float* __restrict__ trans, const float* __restrict__ w1,
@@ -88,7 +86,7 @@ __global__ __launch_bounds__(256, 2) void pn_trunk_kernel(const float* __restric
         __syncthreads();                      // every wave has read h1
 #pragma unroll
         for (int v = 0; v < 16; ++v) {
-            const int c = wave * 32 + pn_row(v, h);
+            const int c = wave * 32 + mfma_row(v, h);
             const float bias = b2[c];
             f32x4 o;
 #pragma unroll
@@ -141,7 +139,7 @@ __global__ __launch_bounds__(256, 2) void pn_trunk_kernel(const float* __restric
         }
         if (j == 0) {
 #pragma unroll
-            for (int v = 0; v < 16; ++v) out[chunk * 32 + pn_row(v, h)] = m[v];
+            for (int v = 0; v < 16; ++v) out[chunk * 32 + mfma_row(v, h)] = m[v];
         }
     }
 }

@@ -16,27 +16,24 @@
 // Also here: the plain fp32 -> pre-split pass (x * x_scale as fp16 hi / lo planes, no normalisation) for a low-resolution
 // operand that no GroupNorm apply pass writes (EfficientUNet's Block.upsample takes the block's output as it is).
 #include "common.h"
+#include "f16x2.h"
 #include "stats_entry.h"
 
 namespace {
 
-typedef _Float16 half8_t __attribute__((ext_vector_type(8)));
-typedef _Float16 half2_t __attribute__((ext_vector_type(2)));
-typedef float float2_t __attribute__((ext_vector_type(2)));
-
-// ---- fp32 [B][C][HW] -> ysp[b][plane][c/8][p][8] (the layout of lc_groupnorm_apply*_split), split rule of conv_f16x2.hip:
-// s = x * x_scale, hi = 11 significant bits truncated (packed toward zero), lo = fp16(s - hi); max |s| -> the range record.
+// ---- fp32 [B][C][HW] -> ysp[b][plane][c/8][p][8] (the layout of lc_groupnorm_apply*_split), split rule of f16x2.h;
+// max |s| -> the range record.
 // Lane = pixel, as norm.hip's gn_apply_split_kernel: a thread owns four pixels 256 apart (32 dword loads in flight) and a wave
 // store instruction covers 1 KiB contiguous of a plane.
 __global__ __launch_bounds__(256) void split_plain_kernel(const float* __restrict__ x, long long x_bs,
-                                                         half8_t* __restrict__ ysp, long long ysp_bs, int C,
+                                                         half8* __restrict__ ysp, long long ysp_bs, int C,
                                                          long long HW, lc_conv_range* range) {
     const int oct = blockIdx.y, b = blockIdx.z;
     const float* xp = x + b * x_bs + (long long)oct * 8 * HW;
     const float xs = range->x_scale;
     const float seen = range->amax_scaled;
-    half8_t* yh = ysp + b * ysp_bs + (long long)oct * HW;
-    half8_t* yl = yh + (long long)(C >> 3) * HW;
+    half8* yh = ysp + b * ysp_bs + (long long)oct * HW;
+    half8* yl = yh + (long long)(C >> 3) * HW;
     float am = 0.0f;
     for (long long tb = blockIdx.x * 1024ll; tb < HW; tb += (long long)gridDim.x * 1024) {
         const long long p = tb + threadIdx.x;
@@ -49,25 +46,17 @@ __global__ __launch_bounds__(256) void split_plain_kernel(const float* __restric
         }
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            half8_t h8, l8;
+            half8 h8, l8;
 #pragma unroll
             for (int k = 0; k < 8; k += 2) {
-                const float s0 = pix[k][i] * xs, s1 = pix[k + 1][i] * xs;
-                am = fmaxf(am, fmaxf(fabsf(s0), fabsf(s1)));
-                const float h0 = __uint_as_float(__float_as_uint(s0) & 0xFFFFE000u);
-                const float h1 = __uint_as_float(__float_as_uint(s1) & 0xFFFFE000u);
-                const half2_t ph = __builtin_bit_cast(half2_t, __builtin_amdgcn_cvt_pkrtz(h0, h1));
-                float2_t r; r.x = s0 - h0; r.y = s1 - h1;
-                const half2_t pl = __builtin_convertvector(r, half2_t);
+                half2v ph, pl;
+                pair_split_scale(pix[k][i], pix[k + 1][i], xs, ph, pl, am);
                 h8[k] = ph.x; h8[k + 1] = ph.y; l8[k] = pl.x; l8[k + 1] = pl.y;
             }
             if (p + 256 * i < HW) { yh[p + 256 * i] = h8; yl[p + 256 * i] = l8; }
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) am = fmaxf(am, __shfl_xor(am, o, 64));
-    if ((threadIdx.x & 63) == 0 && am > seen)
-        atomicMax(reinterpret_cast<unsigned*>(&range->amax_scaled), __float_as_uint(am));
+    publish_amax(range, am, seen);
 }
 
 // ---- the combine pass.  One wave = (sample, output channel, 128-column segment of the low-resolution plane); lane l owns
@@ -252,7 +241,7 @@ extern "C" int lc_split_act_fwd(const float* x, int64_t x_bs, void* y_split, int
     long long gx = (HW + 1023) / 1024;
     while (gx > 1 && gx * (C / 8) * B > 8192) gx = (gx + 1) / 2;
     hipLaunchKernelGGL(split_plain_kernel, dim3((unsigned)gx, C / 8, B), dim3(256), 0, lc_s(s), x, (long long)x_bs,
-                       reinterpret_cast<half8_t*>(y_split), (long long)2 * (C / 8) * HW, C, HW, range);
+                       reinterpret_cast<half8*>(y_split), (long long)2 * (C / 8) * HW, C, HW, range);
     return lc_launch_status();
 }
 

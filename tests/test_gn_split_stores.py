@@ -169,6 +169,17 @@ def test_gn_apply_split_planes(dev, C, G, H, W, route, act, adagn, affine, wide)
     assert abs(amax - want) <= 2e-6 * want
 
 
+def _split_oracle(s):
+    """The split rule of csrc/f16x2.h on s [B, C, HW] (fp32, scale applied) -> the planes' units [B 2 (C/8) HW, 8] fp16."""
+    B, C, HW = s.shape
+    hi = (s.view(torch.int32) & ~0x1FFF).view(torch.float32)
+    lo = (s - hi).half()                 # of the masked fp32 value, not of the packed one
+    h16 = hi.clamp(-65504.0, 65504.0).half()   # hi is packed toward zero: saturating (never inf) above fp16's largest, ...
+    up = h16.float().abs() > hi.abs()    # ... exact for normal fp16, one step down where it rounded up
+    h16 = torch.where(up, (h16.view(torch.int16) - 1).view(torch.float16), h16)
+    return torch.stack((h16, lo), 1).view(B, 2, C // 8, 8, HW).permute(0, 1, 2, 4, 3).reshape(-1, 8)
+
+
 # (C, H, W, wide): lc_split_act_fwd takes planes of a multiple of 4 pixels
 PLAIN_CASES = [(16, 4, 68, False), (32, 2, 1030, False), (16, 4, 256, True), (16, 1, 4, False), (32, 8, 516, False),
                (16, 8, 516, True), (16, 40, 256, False)]
@@ -189,12 +200,54 @@ def test_split_plain_planes_are_exact(dev, C, H, W, wide):
           "lc_split_act_fwd")
     torch.cuda.synchronize()
     s = x.contiguous() * XS
-    hi = (s.view(torch.int32) & ~0x1FFF).view(torch.float32)
-    lo = (s - hi).half()
-    h16 = hi.half()                      # hi is packed toward zero: exact for normal fp16, one step down where it rounded up
-    up = h16.float().abs() > hi.abs()
-    h16 = torch.where(up, (h16.view(torch.int16) - 1).view(torch.float16), h16)
-    want = torch.stack((h16, lo), 1).view(B, 2, C // 8, 8, HW).permute(0, 1, 2, 4, 3).reshape(-1, 8)
+    want = _split_oracle(s)
     assert torch.equal(body, want)
     _check_margin(buf)
     assert float(rng[2]) == float(s.abs().max())
+
+
+def _edge_values():
+    """64 scaled values s, none NaN or inf, every class of the rule with its negative counterpart."""
+    full = 2.0 - 2.0 ** -23              # all 24 significand bits set
+    pos = [0.0,
+           2.0 ** -30 * (1 + 2.0 ** -20), 1.5 * 2.0 ** -27, full * 2.0 ** -27,            # below 2^-25: hi and lo are zero
+           2.0 ** -24, 2.0 ** -20 * (1 + 2.0 ** -10), 1.2345 * 2.0 ** -15, 2.0 ** -17 + 2.0 ** -30,   # hi subnormal in fp16
+           2.0 ** -14 - 2.0 ** -30, 2.0 ** -14 * (1 + 2.0 ** -12), 2.0 ** -3 * (1 + 2.0 ** -22),     # lo subnormal / zero
+           full * 2.0 ** -10, full * 2.0 ** -3, full, full * 2.0 ** 5, full * 2.0 ** 10, full * 2.0 ** 14, full * 2.0 ** 15,
+           65504.0,
+           65504.0 + 2.0 ** -8, 65536.0, 65536.0 + 2.0 ** -7, 70000.0, full * 2.0 ** 16,  # above: hi saturates
+           1.0, 1.5, 3.0, 2047.0, 1027.0 * 2.0 ** -5,                                     # exact in 11 bits: lo is zero
+           0.3, 7.77, 1234.567]
+    assert len(pos) == 32
+    return torch.tensor(pos + [-v for v in pos], dtype=torch.float64).float()
+
+
+def test_split_plain_edge_values(dev):
+    """The rule at its edges (csrc/f16x2.h): signed zeros, s below 2^-25 (hi and lo zero), hi / lo in fp16's subnormal
+    range, full significands, s = +-65504, s above it (hi saturates at +-65504, lo of the masked value), values exact in
+    11 bits (lo +-0) -- through both lanes of a pair (channel c starts the list at value c).  Bit equality of both planes
+    (signed zeros included), untouched margins, the range record = max |s|."""
+    from lidarcrafter_amd import ops as K
+    from lidarcrafter_amd._lib import check, lib
+
+    B, C, H, W = 1, 16, 1, 64
+    sv = _edge_values()
+    idx = (torch.arange(W)[None, :] + torch.arange(C)[:, None]) % W
+    x = (sv[idx] / XS).view(B, C, W).to(dev)              # a power-of-two scale: x * XS is sv again
+    assert bool(torch.isfinite(x).all())
+    buf, body = _planes(B, C, W, dev)
+    rng = _range(dev)
+    check(lib().lc_split_act_fwd(x.data_ptr(), x.stride(0), body.data_ptr(), B, C, H, W, rng.data_ptr(), K._stream()),
+          "lc_split_act_fwd")
+    torch.cuda.synchronize()
+    s = x * XS
+    assert torch.equal(s.cpu().view(torch.int32), sv[idx].view(B, C, W).view(torch.int32))
+    want = _split_oracle(s)
+    assert bool(torch.isfinite(want.float()).all()) and float(want.float().abs().max()) == 65504.0
+    got, exp = body.view(torch.int16).cpu(), want.view(torch.int16).cpu()
+    bad = (got != exp).nonzero()
+    for u, k in bad[:16].tolist():
+        print(f"unit {u} elem {k}: got {int(got[u, k]) & 0xFFFF:#06x} want {int(exp[u, k]) & 0xFFFF:#06x}")
+    assert torch.equal(got, exp), f"{len(bad)} of {got.numel()} halves differ"
+    _check_margin(buf)
+    assert float(rng[2]) == float(s.abs().max()) == float(sv.abs().max())
