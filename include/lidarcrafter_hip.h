@@ -1023,6 +1023,32 @@ int lc_spvox_devoxelize(const float* f, int64_t ldf, int n_rows, const int32_t* 
 int lc_spvox_voxelize(const float* f, int64_t ldf, int n_rows, const int32_t* perm, int n_perm, const int32_t* offsets,
                       int V, float* out, int64_t ldo, int C, lc_stream_t s);
 
+/* ---------------------------------------------------------------------------------------------
+ * Dense convolutions of RangeNet-53 / -21 (csrc/rangenet.hip): the extractor of the Frechet Range
+ * Image Distance (lidargen/metrics/models/rangenet/model.py) and of FRD (lidargen/metrics/extractor/rangenet.py).
+ * Contiguous float32 NCHW tensors, zero padding, exact fp32 on the f32-input MFMA, no atomics; a sample's bits do not depend
+ * on the batch it is in.
+ *   mode 0: 1x1            mode 1: 3x3, padding (1,1)            mode 2: 3x3, stride (1,2), padding (1,1), W_out = (W-1)/2+1
+ *   mode 3: transposed 1x4, stride (1,2), padding (0,1), W_out = 2 W: output column 2j = w[1] x[j] + w[3] x[j-1], column
+ *           2j+1 = w[2] x[j] + w[0] x[j+1]
+ *   y = acc + bias[co]; act: y = y > 0 ? y : 0.1f y; y += res1; y += res2 (res1, res2 [B,Co,H,W_out] or NULL).
+ *   k order: input channels in chunks of 16 (mode 0: 32) ascending, inside a chunk tap ascending (ky*3+kx; mode 3: 1, 3, 2,
+ *   0), inside a tap channel ascending; every chunk is an fma chain from zero, the chunks are added in ascending order.
+ * lc_rangenet_pack_weight works on HOST memory: w [Co,Ci,kh,kw] (mode 3: [Ci,Co,1,4]) -> out,
+ * lc_rangenet_packed_weight_elems(mode, Ci, Co) floats (0 for arguments it does not take), zero-filled past Ci and Co.
+ * wpk must be 16-byte aligned (LC_EUNSUP); y may not alias x, res1 or res2 (LC_EINVAL); B * ceil(Co / 128) <= 65535 and
+ * H <= 131070 (LC_EUNSUP).  lc_rangenet_tile_extent(i): 0 pixels per wave, 1 rows per block, 2 channels per wave, 3 the
+ * widest block row in pixels (Co <= 32).
+ *   lc_rangenet_reduce_fwd: kind 0 out[b, c] = mean over the map; 1 out[b, 16 c + n] = mean over all rows and columns
+ *   n W/16 .. (n+1) W/16 - 1 (W % 16 == 0, LC_EUNSUP otherwise); 2 the same over rows n H/16 .. (H % 16 == 0).  One wave per
+ *   output, lane-strided partial sums then a butterfly: a fixed order. */
+int lc_rangenet_tile_extent(int which);
+int64_t lc_rangenet_packed_weight_elems(int mode, int Ci, int Co);
+int lc_rangenet_pack_weight(const float* w, int mode, int Ci, int Co, float* out);
+int lc_rangenet_conv_fwd(const float* x, const float* wpk, const float* bias, const float* res1, const float* res2, float* y,
+                         int B, int Ci, int Co, int H, int W, int mode, int act, lc_stream_t s);
+int lc_rangenet_reduce_fwd(const float* x, float* out, int B, int C, int H, int W, int kind, lc_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -206,6 +206,11 @@ SIGNATURES = {
     "lc_spvox_query": (i32, [vp, i32, i32, vp, i32, vp, vp, vp]),
     "lc_spvox_devoxelize": (i32, [vp, i64, i32, vp, vp, vp, i64, vp, i64, i32, i32, vp]),
     "lc_spvox_voxelize": (i32, [vp, i64, i32, vp, i32, vp, i32, vp, i64, i32, vp]),
+    "lc_rangenet_tile_extent": (i32, [i32]),
+    "lc_rangenet_packed_weight_elems": (i64, [i32, i32, i32]),
+    "lc_rangenet_pack_weight": (i32, [vp, i32, i32, i32, vp]),
+    "lc_rangenet_conv_fwd": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
+    "lc_rangenet_reduce_fwd": (i32, [vp, vp, i32, i32, i32, i32, i32, vp]),
 }
 
 _lib = None

@@ -2,8 +2,9 @@
 Frechet Point Distance (`extractor.pointnet`, `distribution`, `eval_utils.compute_fpd`), the Frechet Sparse Volume
 Distance (`models.minkowskinet`, `metric_utils.compute_logits`, `eval_utils.compute_fsvd`; sparse 3-D convolution in
 csrc/spconv.hip) and the Frechet Point-Voxel Distance (`models.spvcnn`, `metric_utils.compute_point_voxel_logits`,
-`eval_utils.compute_fpvd`; point <-> voxel exchanges in csrc/spvoxel.hip).  The fourth learned-feature metric of the
-reference (FRID: RangeNet) is not built."""
+`eval_utils.compute_fpvd`; point <-> voxel exchanges in csrc/spvoxel.hip) and the Frechet Range Image Distance
+(`models.rangenet`, `metric_utils.compute_range_logits`, `eval_utils.compute_frid`; dense convolutions in
+csrc/rangenet.hip), with its sibling FRD of the reference's own evaluator (`extractor.rangenet`, `eval_utils.compute_frd`)."""
 import os
 
 # a score line as the reference prints it: a 50-column rule above and below `|<16 blanks>NAME:1.2345E+00<17 blanks>|`
@@ -48,17 +49,41 @@ def _load_pretrained(who, dataset_name, model_name, model_cls, device, root):
     return model.to(device)
 
 
+def _load_rangenet(dataset_name, device, root):
+    import yaml
+
+    from .models.rangenet.model import Model
+
+    folder = os.path.join(DEFAULT_ROOT if root is None else os.fspath(root), dataset_name, "rangenet")
+    if not os.path.isdir(folder):
+        raise FileNotFoundError(f"build_model: no pretrained weights folder at {folder} -- place the reference's "
+                                "config.yaml, backbone and segmentation_decoder there or pass root=<path>; this build "
+                                "does not fetch them")
+    for n in ("config.yaml", "backbone", "segmentation_decoder"):
+        if not os.path.isfile(os.path.join(folder, n)):
+            raise FileNotFoundError(f"build_model: {os.path.join(folder, n)} is missing; this build does not fetch it")
+    with open(os.path.join(folder, "config.yaml"), "r") as f:
+        model = Model(yaml.safe_load(f))
+    model.load_pretrained_weights(folder)
+    model.eval().requires_grad_(False)
+    return model.to(device)
+
+
 def build_model(dataset_name, model_name, device="cpu", root=None):
     """The pretrained extractor `model_name` of `dataset_name` from <root>/<dataset_name>/<model_name>/{config.yaml,
-    model.ckpt} (root: DEFAULT_ROOT), in eval mode on `device`.  Only 'minkowskinet' is built here ('spvcnn' has its own
-    loader, models.spvcnn.pretrained).  Nothing is fetched: a missing folder or file raises FileNotFoundError naming the
+    model.ckpt} (root: DEFAULT_ROOT), in eval mode on `device`.  'minkowskinet' is built here and 'rangenet' (config.yaml
+    and the state dicts `backbone` and `segmentation_decoder` of its folder); 'spvcnn' has its own loader,
+    models.spvcnn.pretrained.  Nothing is fetched: a missing folder or file raises FileNotFoundError naming the
     path.  Unlike the reference's `strict=False` a model key missing from the checkpoint raises; keys the model does not
     have are ignored."""
     if model_name == "spvcnn":
         raise NotImplementedError("build_model: 'spvcnn' is not dispatched from here; the extractor of FPVD is loaded by "
                                   "models.spvcnn.pretrained(dataset_name, device, root)")
+    if model_name == "rangenet":
+        return _load_rangenet(dataset_name, device, root)
     if model_name != "minkowskinet":
-        raise NotImplementedError(f"build_model: '{model_name}' is not built (only 'minkowskinet', the extractor of FSVD)")
+        raise NotImplementedError(f"build_model: '{model_name}' is not built (only 'minkowskinet', the extractor of FSVD, "
+                                  "and 'rangenet', the extractor of FRID)")
     from .models.minkowskinet.model import Model
 
     return _load_pretrained("build_model", dataset_name, model_name, Model, device, root)

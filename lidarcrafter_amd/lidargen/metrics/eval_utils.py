@@ -3,12 +3,14 @@ metrics, data)` and the weight-free scores behind it (`compute_cd` :40-51, `comp
 `compute_jsd` :85-95).  Every score is printed through the reference's OUTPUT_TEMPLATE and also returned; `evaluate`
 returns {metric: score}.  Of the perceptual metrics FSVD and FPVD are built (`compute_fd` :98-102, `compute_fsvd` :116-124:
 MinkUNet features, sparse convolution in csrc/spconv.hip; `compute_fpvd` :127-135: SPVCNN features, point <-> voxel
-exchanges in csrc/spvoxel.hip); FRID is not.  `evaluate` still refuses all three and 'mmd' (its callers rely on that):
-call `compute_fsvd` / `compute_fpvd` / `compute_mmd` directly.
+exchanges in csrc/spvoxel.hip) and FRID (`compute_frid` :105-113: RangeNet features of range images, dense convolutions
+in csrc/rangenet.hip).  `evaluate` still refuses all three and 'mmd' (its callers rely on that): call `compute_frid` /
+`compute_fsvd` / `compute_fpvd` / `compute_mmd` directly.
 
 `extract_point_features` / `compute_fpd` are the Frechet Point Distance of the reference's own evaluator
 (tools/evaluation/evaluate_our.py `EvaluationEngine`: PointNet1 features of every cloud, `distribution.
-compute_frechet_distance` on the two feature sets); `evaluate` does not dispatch them."""
+compute_frechet_distance` on the two feature sets); `extract_range_features` / `compute_frd` are its FRD (RangeNet
+'lidargen' features of 5-channel range images).  `evaluate` does not dispatch them."""
 from __future__ import annotations
 
 import numpy as np
@@ -19,7 +21,7 @@ from . import distribution, metric_utils
 from .chamfer import bev_min_matching, compute_pairwise_cd
 from .emd import compute_pairwise_emd_batch
 
-_NOT_BUILT = {"frid": "the pretrained range-image extractor",
+_NOT_BUILT = {"frid": "a direct call of eval_utils.compute_frid(reference, samples, data)",
               "fpvd": "a direct call of eval_utils.compute_fpvd(reference, samples, data)",
               "fsvd": "a direct call of eval_utils.compute_fsvd(reference, samples, data)",
               "mmd": "a direct call of eval_utils.compute_mmd(reference, samples, data)"}
@@ -29,9 +31,7 @@ def evaluate(reference, samples, metrics, data):
     scores = {}
     for m in ("frid", "fsvd", "fpvd"):   # perceptual
         if m in metrics:
-            if m in ("fsvd", "fpvd"):
-                raise NotImplementedError(f"evaluate: metric '{m}' is not dispatched from here; it needs {_NOT_BUILT[m]}")
-            raise NotImplementedError(f"evaluate: metric '{m}' needs {_NOT_BUILT[m]}, which this build does not have")
+            raise NotImplementedError(f"evaluate: metric '{m}' is not dispatched from here; it needs {_NOT_BUILT[m]}")
     if "mmd" in metrics:
         raise NotImplementedError(f"evaluate: metric 'mmd' is not dispatched from here; it needs {_NOT_BUILT['mmd']}")
     # reconstruction
@@ -162,4 +162,52 @@ def compute_fpvd(reference, samples, data, model=None):
     gt_logits, samples_logits = metric_utils.compute_point_voxel_logits(data, reference, samples, model=model)
     score = compute_fd(gt_logits, samples_logits)
     print(OUTPUT_TEMPLATE.format("FPVD", score))
+    return score
+
+
+def compute_frid(reference, samples, data, model=None, size=None):
+    """Score of Frechet Range Image Distance (FRID): the Frechet distance of the row-band means of RangeNet's decoder map
+    over the range images of the two sets of [N, 3] clouds.  `model`: the extractor to use instead of the pretrained one;
+    `size`: (H, W) of the range images instead of the dataset's."""
+    print("Evaluating (FRID) ...")
+    gt_logits, samples_logits = metric_utils.compute_range_logits(data, reference, samples, model=model, size=size)
+    score = compute_fd(gt_logits, samples_logits)
+    print(OUTPUT_TEMPLATE.format("FRID", score))
+    return score
+
+
+def extract_range_features(model, preprocess, imgs, masks=None, batch_size=16):
+    """'lidargen' features of `model` (extractor.rangenet.RangeNet, eval mode, on the GPU) for [n, C, H, W] range images
+    (a CUDA tensor or a numpy array; `masks` [n, 1, H, W] or None) -> [n, 4096] float64 numpy array, `batch_size` images
+    at a time through `preprocess` (extractor.rangenet.Preprocess; None: the images as they are)."""
+    if isinstance(imgs, np.ndarray):
+        if not torch.cuda.is_available():
+            raise RuntimeError("extract_range_features needs the MI355X: no CPU fallback on the hot path")
+        imgs = torch.from_numpy(np.ascontiguousarray(imgs, np.float32)).cuda()
+    elif not isinstance(imgs, torch.Tensor) or not imgs.is_cuda:
+        raise RuntimeError("extract_range_features: tensors must be CUDA(HIP) tensors -- no CPU fallback on the hot path")
+    if masks is not None:
+        masks = torch.as_tensor(masks).to(imgs.device).float()
+    rows = []
+    with torch.no_grad():
+        for lo in range(0, imgs.shape[0], batch_size):
+            x = imgs[lo:lo + batch_size].float()
+            if preprocess is not None:
+                x = preprocess(x, None if masks is None else masks[lo:lo + batch_size])
+            rows.append(model(x, feature="lidargen").double().cpu().numpy())
+    return np.concatenate(rows) if rows else np.zeros((0, 0))
+
+
+def compute_frd(reference, samples, model, preprocess=None, batch_size=16, columns=None):
+    """Score of Frechet Range Distance (FRD) of the reference's own evaluator: the Frechet distance of the RangeNet
+    'lidargen' features of the two sets of range images.  Either set may be a feature matrix ([n, width] numpy array)
+    instead of [n, C, H, W] images.  `columns` (a slice or index array) restricts the distance to those feature columns."""
+    print("Evaluating (FRD) ...")
+    feats = [a if isinstance(a, np.ndarray) and a.ndim == 2 else extract_range_features(model, preprocess, a,
+                                                                                         batch_size=batch_size)
+             for a in (reference, samples)]
+    if columns is not None:
+        feats = [f[:, columns] for f in feats]
+    score = distribution.compute_frechet_distance(feats[0], feats[1])
+    print(OUTPUT_TEMPLATE.format("FRD ", score))
     return score

@@ -7,8 +7,10 @@ unique voxels come from a device radix sort (lc_sparse_quantize).  numpy in -> n
 tensors in -> CUDA tensors out.  Of the feature-extractor front-ends of that module the sparse-volume one is built
 (`preprocess_pcd` :310-314, `pcd2voxel` :157-167, a collate, `compute_logits` :374-412 for 'voxel' with the depth-sector
 aggregation of `batch2list` :351-365 on the device) and the point-voxel one (`compute_point_voxel_logits`: the same
-input and aggregation around the SPVCNN); pcd2range and the 'range' modality are not.  `compute_logits` still refuses
-'point_voxel' by name (its callers rely on that) and points at `compute_point_voxel_logits`."""
+input and aggregation around the SPVCNN) and the range-image one (`pcd2range` :69-122, `range2xyz` :125-154,
+`preprocess_range` :317-322 in numpy on the host, `compute_range_logits`: RangeNet over 5-channel range images, row-band
+means on the device).  `compute_logits` still refuses 'point_voxel' and 'range' by name (its callers rely on that) and
+points at `compute_point_voxel_logits` / `compute_range_logits`."""
 from __future__ import annotations
 
 import math
@@ -207,7 +209,8 @@ def _sector_features(data_type, modality, model, sets):
 def compute_logits(data_type, modality, *args, model=None, root=None):
     """For every list of [N, 3] clouds in `args` the float32 [n, 16 * width] matrix of depth-sector means of the
     extractor's features (metric_utils.py:374-412), MODAL2BATCHSIZE clouds at a time.  Only 'voxel' (MinkowskiNet, FSVD)
-    is dispatched from here; 'point_voxel' (SPVCNN, FPVD) is `compute_point_voxel_logits`.  `model`: a minkowskinet Model
+    is dispatched from here; 'point_voxel' (SPVCNN, FPVD) is `compute_point_voxel_logits`, 'range' (RangeNet, FRID) is
+    `compute_range_logits`.  `model`: a minkowskinet Model
     in eval mode on the GPU; None builds the pretrained one (build_model)."""
     from . import MODALITY2MODEL, TYPE2DATASET, build_model
 
@@ -217,8 +220,8 @@ def compute_logits(data_type, modality, *args, model=None, root=None):
         raise NotImplementedError(f"compute_logits: modality '{modality}' ({MODALITY2MODEL[modality]}) is not dispatched "
                                   "from here; call metric_utils.compute_point_voxel_logits(data_type, *sets)")
     if modality != "voxel":
-        raise NotImplementedError(f"compute_logits: modality '{modality}' ({MODALITY2MODEL[modality]}) is not built; "
-                                  "'voxel' is, and 'point_voxel' through compute_point_voxel_logits")
+        raise NotImplementedError(f"compute_logits: modality '{modality}' ({MODALITY2MODEL[modality]}) is not dispatched "
+                                  "from here; call metric_utils.compute_range_logits(data_type, *sets)")
     if not torch.cuda.is_available():
         raise RuntimeError("compute_logits needs the MI355X: no CPU fallback on the hot path")
     if model is None:
@@ -241,3 +244,91 @@ def compute_point_voxel_logits(data_type, *sets, model=None, root=None):
     if model is None:
         model = spvcnn.pretrained(TYPE2DATASET[data_type], device="cuda", root=root)
     return _sector_features(data_type, "point_voxel", model, sets)
+
+
+# ---- the range-image front-end (FRID) -----------------------------------------------------------------------------
+def pcd2range(pcd, size, fov, depth_range, remission=None, labels=None, **kwargs):
+    """One cloud [N, 3] -> (float32 [H, W] depth image with -1 where no point falls, feature image or None): spherical
+    projection, the nearest point of a pixel wins (metric_utils.py:69-122).  numpy on the host, in the cloud's dtype."""
+    fov_up, fov_down = fov[0] / 180.0 * np.pi, fov[1] / 180.0 * np.pi
+    fov_range = abs(fov_down) + abs(fov_up)
+    depth = np.linalg.norm(pcd, 2, axis=1)
+    mask = np.logical_and(depth > depth_range[0], depth < depth_range[1])
+    depth, pcd = depth[mask], pcd[mask]
+    yaw = -np.arctan2(pcd[:, 1], pcd[:, 0])
+    pitch = np.arcsin(pcd[:, 2] / depth)
+    proj_x = 0.5 * (yaw / np.pi + 1.0)
+    proj_y = 1.0 - (pitch + abs(fov_down)) / fov_range
+    proj_x *= size[1]
+    proj_y *= size[0]
+    proj_x = np.maximum(0, np.minimum(size[1] - 1, np.floor(proj_x))).astype(np.int32)
+    proj_y = np.maximum(0, np.minimum(size[0] - 1, np.floor(proj_y))).astype(np.int32)
+    order = np.argsort(depth)[::-1]                      # far first: the nearest point is written last
+    proj_x, proj_y, depth = proj_x[order], proj_y[order], depth[order]
+    proj_range = np.full(size, -1, dtype=np.float32)
+    proj_range[proj_y, proj_x] = depth
+    proj_feature = None
+    if remission is not None:
+        proj_feature = np.full(size, -1, dtype=np.float32)
+        proj_feature[proj_y, proj_x] = remission[mask][order]
+    elif labels is not None:
+        proj_feature = np.full(size, 0, dtype=np.float32)
+        proj_feature[proj_y, proj_x] = labels[mask][order]
+    return proj_range, proj_feature
+
+
+def range2xyz(range_img, fov, depth_range, depth_scale=None, log_scale=True, **kwargs):
+    """[H, W] depth image -> float64 [3, H, W] points of the pixel centres' rays, -1 where the depth is outside
+    `depth_range` (metric_utils.py:125-154).  `depth_scale` is read only with `log_scale` (depth = 2^(img * scale) - 1);
+    it has a default here because the nuScenes settings carry none and preprocess_range never uses it."""
+    size = range_img.shape
+    fov_up, fov_down = fov[0] / 180.0 * np.pi, fov[1] / 180.0 * np.pi
+    fov_range = abs(fov_down) + abs(fov_up)
+    depth = (np.exp2(range_img * depth_scale) - 1) if log_scale else range_img
+    scan_x, scan_y = np.meshgrid(np.arange(size[1]), np.arange(size[0]))
+    scan_x = scan_x.astype(np.float64) / size[1]
+    scan_y = scan_y.astype(np.float64) / size[0]
+    yaw = np.pi * (scan_x * 2 - 1)
+    pitch = (1.0 - scan_y) * fov_range - abs(fov_down)
+    xyz = -np.ones((3, *size))
+    xyz[0] = np.cos(yaw) * np.cos(pitch) * depth
+    xyz[1] = -np.sin(yaw) * np.cos(pitch) * depth
+    xyz[2] = np.sin(pitch) * depth
+    mask = np.logical_and(depth > depth_range[0], depth < depth_range[1])
+    xyz[:, ~mask] = -1
+    return xyz
+
+
+def preprocess_range(pcd, **kwargs):
+    """One cloud -> float64 [4, H, W]: the depth image on top of its back-projection (metric_utils.py:317-322)."""
+    depth_img = pcd2range(pcd, **kwargs)[0]
+    xyz_img = range2xyz(depth_img, log_scale=False, **kwargs)
+    return np.vstack([depth_img[None], xyz_img])
+
+
+def compute_range_logits(data_type, *sets, model=None, root=None, size=None):
+    """For every list of [N, 3] clouds in `sets` the float32 [n, 16 * 32 = 512] matrix of row-band means of RangeNet's
+    decoder map over the clouds' range images (the reference's compute_logits for 'range'), MODAL2BATCHSIZE['range']
+    clouds at a time.  The projection runs in numpy on the host.  `model`: a models.rangenet Model in eval mode on the
+    GPU; None loads the pretrained one (build_model).  `size`: (H, W) instead of the dataset's image size."""
+    from . import AGG_TYPE, DATASET_CONFIG, MODAL2BATCHSIZE, TYPE2DATASET, build_model
+
+    assert data_type in ["32", "64"]
+    if not torch.cuda.is_available():
+        raise RuntimeError("compute_range_logits needs the MI355X: no CPU fallback on the hot path")
+    cfg = dict(DATASET_CONFIG[TYPE2DATASET[data_type]])
+    if size is not None:
+        cfg["size"] = [int(size[0]), int(size[1])]
+    if model is None:
+        model = build_model(TYPE2DATASET[data_type], "rangenet", device="cuda", root=root)
+    bs = MODAL2BATCHSIZE["range"]
+    dev = next(model.parameters()).device
+    output = tuple()
+    for data in sets:
+        rows = []
+        for i in range(math.ceil(len(data) / bs)):
+            batch = np.stack([preprocess_range(np.asarray(pcd), **cfg) for pcd in data[i * bs:(i + 1) * bs]])
+            with torch.no_grad():
+                rows.append(model(torch.from_numpy(batch).float().to(dev), return_final_logits=True, agg_type=AGG_TYPE))
+        output += (np.vstack(rows) if rows else np.zeros((0, 0), np.float32),)
+    return output

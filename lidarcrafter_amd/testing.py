@@ -370,3 +370,48 @@ def synth_scene_graph_batch(n_scenes: int, seed: int, manipulate: bool = False) 
         out[name] = c
     out.update(missing_nodes=missing, manipulated_subs=man_s, manipulated_objs=man_o)
     return {"scenegraph_input": out}
+
+
+@torch.no_grad()
+def seeded_fill_rangenet(module: torch.nn.Module, salt: int = 0) -> torch.nn.Module:
+    """Seeded weights that keep a 53-layer random RangeNet (either module tree) in range, keyed by state_dict name: conv
+    weights N(0, 1 / fan_in), conv biases 0.1 N, BatchNorm gains in U(0.5, 1.5) -- times 0.35 on the second BatchNorm of
+    every residual block (`...bn2.weight` / `...residual.1.1.weight`), whose output is added to the block's input --
+    BatchNorm biases and running means 0.2 N, running variances in U(0.5, 1.5).  With `rangenet_images` the decoder map
+    peaks near 1e2 and every feature column varies; a He gain reaches 1e8 over the 52 convolutions."""
+    for key, p in list(module.named_parameters()) + list(module.named_buffers()):
+        if key.endswith("num_batches_tracked"):
+            continue
+        g = _gen_for(key, salt)
+        if p.ndim == 4:
+            v = torch.randn(p.shape, generator=g) / max(1, p.numel() // p.shape[0]) ** 0.5
+        elif key.endswith("running_var"):
+            v = 0.5 + torch.rand(p.shape, generator=g)
+        elif key.endswith("running_mean"):
+            v = 0.2 * torch.randn(p.shape, generator=g)
+        elif key.endswith("weight"):                       # BatchNorm gains
+            v = 0.5 + torch.rand(p.shape, generator=g)
+            if key.endswith("bn2.weight") or key.endswith("residual.1.1.weight"):
+                v = 0.35 * v
+        elif ".bn" in key or key.startswith("bn") or key.endswith(".1.bias") and "head" not in key:
+            v = 0.2 * torch.randn(p.shape, generator=g)    # BatchNorm biases
+        else:
+            v = 0.1 * torch.randn(p.shape, generator=g)    # conv biases (up convs, head)
+        p.copy_(v.to(device=p.device, dtype=p.dtype))
+    return module
+
+
+def rangenet_images(B: int, H: int, W: int, seed: int, holes: float = 0.15) -> torch.Tensor:
+    """[B, 5, H, W] float32 range images as the evaluator feeds them: (depth, x, y, z, remission), depth in 8 .. 40 m along
+    the pixel's ray (azimuth over the columns, +10 .. -30 degrees over the rows), remission in [0, 1), and -1 in every
+    channel of the `holes` share of the pixels that saw nothing."""
+    import math
+
+    g = torch.Generator().manual_seed(seed)
+    depth = 8.0 + 32.0 * torch.rand((B, 1, H, W), generator=g)
+    yaw = math.pi * (2.0 * (torch.arange(W, dtype=torch.float32) + 0.5) / W - 1.0).view(1, 1, 1, W)
+    pitch = math.radians(10.0) - math.radians(40.0) * ((torch.arange(H, dtype=torch.float32) + 0.5) / H).view(1, 1, H, 1)
+    img = torch.cat([depth, depth * torch.cos(yaw) * torch.cos(pitch), -depth * torch.sin(yaw) * torch.cos(pitch),
+                     depth * torch.sin(pitch).expand(1, 1, H, W), torch.rand((B, 1, H, W), generator=g)], dim=1)
+    hole = torch.rand((B, 1, H, W), generator=g) < holes
+    return torch.where(hole, torch.full_like(img, -1.0), img).contiguous()
