@@ -380,6 +380,30 @@ int lc_attention_f16x2_fwd(const lc_cm_operand* q, const lc_cm_operand* q_pos,
                            int64_t o_bs, int64_t o_hs, int64_t o_cs, int B, int heads, int Lq,
                            int Lk0, int Lk1, int dqk, int dpos, int dv, float scale,
                            lc_stream_t s);
+/* Which kernel a call runs (pure host code, no GPU needed; the launchers switch on the same function, csrc/attention_route.h).
+ * lc_attention_route: the forward entries.  split: 1 for lc_attention_f16x2_fwd and lc_attention_train_fwd(f16x2 = 1);
+ *   has_amax: lc_attention_train_fwd with qkv_amax; bh = B * heads; waves_env: an LC_ATTN_WAVES value (0 = unset), or < 0
+ *   for the value this process cached.  lc_attention_bwd_route: lc_attention_bwd (split 0) / lc_attention_bwd_f16x2 (1).
+ * Both return  family << 16 | DQK << 8 | NDV << 4 | (waves == 8) << 1 | PRE  with family 1 fp32 forward (attn_kernel),
+ *   2 f16x2-split forward (attn_h_kernel), 3 fp32 backward, 4 split backward; DQK = 32 / 64 and NDV = 1 / 2 the
+ *   instantiated q / k channel count and 32-channel blocks of v; PRE = 1: pre-scales from the measured maxima.
+ *   The codes of the entries where they refuse: LC_EINVAL for bh <= 0, Lq <= 0, dpos < 0; LC_EUNSUP for dqk <= 0,
+ *   dqk + dpos > 64, dv <= 0, dv > 64, B * heads > 65535 (the grid's y extent).
+ * A split request goes to the fp32 kernels when dqk % 8 or dpos % 8: the split kernel stages K in units of 8 channel
+ * rows of ONE operand without a per-channel guard.
+ * Range contract of the inference split routes (lc_attention_f16x2_fwd, lc_attention_units_fwd and the units the qkv
+ * projection writes): the operands are split with the CONSTANT pre-scale 16.  With m_q = max|q * scale * log2(e)|,
+ * m_k = max|k|, m_v = max|v| (every positional part and second segment included):
+ *   representable  16 * m in [4, 32768), i.e. 0.25 <= m < 2048, for each of m_q, m_k, m_v: nothing saturates, the
+ *                  result is finite and no worse than 4 x the error of the same attention evaluated in float32;
+ *   accurate       the tolerance of lc_attention_fwd (2e-6 rel-L2 against float64) holds where, in addition,
+ *                  m_q * m_k <= 32 / sqrt(dqk + dpos): scores that deviate by about one nat over the keys.  With both
+ *                  operands representable this ends at m = 128 / sqrt(dqk + dpos) for q and k; m_v may be anywhere
+ *                  in its window.  With sharper scores float32 itself comes to that tolerance or past it.
+ * Outside the representable window the result loses accuracy (below) or saturates (above) silently;
+ * lc_attention_fwd and the training entry (measured pre-scales) have no such window. */
+int lc_attention_route(int split, int has_amax, int dqk, int dpos, int dv, int64_t bh, int Lq, int waves_env);
+int lc_attention_bwd_route(int split, int dqk, int dv, int64_t bh);
 /* MeanFlow generator (MFEfficientUNet, lidargen/models/unets/efficient_mf_unet.py; csrc/flow.hip).
  * lc_qk_norm_cm_fwd: in place, per (sample b, head h, token t) of the channel-major q and k operands -- the q / k
  *   channel slices of the qkv projection's [B, 3C, L] output -- the d channels h*d .. h*d+d-1 (channel stride q_cs / k_cs,

@@ -18,6 +18,7 @@
 
 #include "common.h"
 #include "attention_split.h"
+#include "attention_route.h"
 
 namespace {
 
@@ -231,10 +232,10 @@ __global__ __launch_bounds__(64 * NW) void attn_h_kernel(AttnArgs a) {
     const float* vp1 = head_ptr(a.v2, b, h);
 
     // staging roles: K unit (cb, key) for tid < NKU; V item (channel c, key octet o) for tid < NVU.
-    // dqk % 8 == 0 (checked by the launcher): the 8 channels of a K unit are all content or all
-    // positional, so each thread keeps ONE base pointer + channel stride per key segment and the
-    // K loop has no per-element address logic.  Threads without a role read a valid dummy
-    // address and store zeros.
+    // dqk % 8 == 0 and dpos % 8 == 0 (lc_attn_route_fwd sends every other call to attn_kernel):
+    // the 8 channels of a K unit are all content or all positional AND all exist, so each thread
+    // keeps ONE base pointer + channel stride per key segment and the K loop has no per-element
+    // address logic or guard.  Threads without a role read a valid dummy address and store zeros.
     static_assert(NW == 4 || (NW == 8 && NKU <= 256 && NVU <= 128), "8 waves: K roles in waves 0-3, V roles in waves 4-5");
     const int k_cb = tid >> 5, k_key = tid & 31;
     const int vt = NW == 8 ? tid - 256 : tid;            // V roles: threads 256 ... 256 + NVU of an 8-wave block
@@ -424,6 +425,12 @@ __global__ __launch_bounds__(64 * NW) void attn_h_kernel(AttnArgs a) {
 
 }  // namespace
 
+// LC_ATTN_WAVES, read once per process: 4 / 8 force the block size of the split inference kernels, unset = by grid size
+static int attn_waves_env() {
+    static const int w = [] { const char* e = getenv("LC_ATTN_WAVES"); return e ? atoi(e) : 0; }();
+    return w;
+}
+
 static int attention_launch(int split, float* lse, const unsigned* qkv_amax, const lc_cm_operand* q, const lc_cm_operand* q_pos,
                                 const lc_cm_operand* k, const lc_cm_operand* k_pos,
                                 const lc_cm_operand* v, const lc_cm_operand* k2,
@@ -437,7 +444,9 @@ static int attention_launch(int split, float* lse, const unsigned* qkv_amax, con
     if (Lk1 > 0 && (!k2 || !v2 || !k2->p || !v2->p)) return LC_EINVAL;
     if (dpos > 0 && (!q_pos || !k_pos || !q_pos->p || !k_pos->p)) return LC_EINVAL;
     if (dpos > 0 && Lk1 > 0 && (!k2_pos || !k2_pos->p)) return LC_EINVAL;
-    if (dqk <= 0 || dqk + dpos > 64 || dv <= 0 || dv > 64) return LC_EUNSUP;
+    // (a shape no kernel takes, B * heads > 65535 -- the grid's y extent -- included: refused before any HIP call)
+    const int route = lc_attn_route_fwd(split, qkv_amax != nullptr, dqk, dpos, dv, (long long)B * heads, Lq, attn_waves_env());
+    if (route < 0) return route;
     const lc_cm_operand none = {nullptr, 0, 0, 0};
     AttnArgs a;
     a.q = *q; a.qp = q_pos ? *q_pos : none; a.k = *k; a.kp = k_pos ? *k_pos : none; a.v = *v;
@@ -447,37 +456,34 @@ static int attention_launch(int split, float* lse, const unsigned* qkv_amax, con
     a.qscale = scale * 1.4426950408889634f;
     a.lse = lse;
     a.qkv_amax = qkv_amax;
-    dim3 grid((Lq + 127) / 128, B * heads);
-    const int dq = (dqk + dpos) <= 32 ? 32 : 64, nd = dv <= 32 ? 1 : 2;
-    if (split && dqk % 8 == 0) {   // (a K unit = 8 channels of ONE operand; else the fp32 kernel)
-        // 256 queries per block (8 waves) where d_v <= 32 and the grid still covers the chip (measured: every such layer
-        // of the layout model and the 512-key self-attention gain 6-14 %; a 300-token batch-2 case loses 12 %)
-        static const int w8_env = [] { const char* e = getenv("LC_ATTN_WAVES"); return e ? atoi(e) : 0; }();
-        const long long blocks8 = (long long)((Lq + 255) / 256) * B * heads;
-        if (qkv_amax) {            // training entry: measured pre-scales
-            if (dq == 32 && nd == 1) hipLaunchKernelGGL((attn_h_kernel<32, 1, 4, true>), grid, dim3(256), 0, lc_s(s), a);
-            else if (dq == 64 && nd == 1) hipLaunchKernelGGL((attn_h_kernel<64, 1, 4, true>), grid, dim3(256), 0, lc_s(s), a);
-            else if (dq == 32 && nd == 2) hipLaunchKernelGGL((attn_h_kernel<32, 2, 4, true>), grid, dim3(256), 0, lc_s(s), a);
-            else hipLaunchKernelGGL((attn_h_kernel<64, 2, 4, true>), grid, dim3(256), 0, lc_s(s), a);
-            return lc_launch_status();
-        }
-        if (nd == 1 && (w8_env == 8 || (w8_env == 0 && blocks8 >= 128))) {
-            dim3 grid8((Lq + 255) / 256, B * heads);
-            if (dq == 32) hipLaunchKernelGGL((attn_h_kernel<32, 1, 8>), grid8, dim3(512), 0, lc_s(s), a);
-            else hipLaunchKernelGGL((attn_h_kernel<64, 1, 8>), grid8, dim3(512), 0, lc_s(s), a);
-            return lc_launch_status();
-        }
-        if (dq == 32 && nd == 1) hipLaunchKernelGGL((attn_h_kernel<32, 1>), grid, dim3(256), 0, lc_s(s), a);
-        else if (dq == 64 && nd == 1) hipLaunchKernelGGL((attn_h_kernel<64, 1>), grid, dim3(256), 0, lc_s(s), a);
-        else if (dq == 32 && nd == 2) hipLaunchKernelGGL((attn_h_kernel<32, 2>), grid, dim3(256), 0, lc_s(s), a);
-        else hipLaunchKernelGGL((attn_h_kernel<64, 2>), grid, dim3(256), 0, lc_s(s), a);
-        return lc_launch_status();
+    const dim3 grid((Lq + 127) / 128, B * heads), grid8((Lq + 255) / 256, B * heads);
+#define LC_ATTN_CASE(FAMILY, DQ, ND, NW, PRE, KERNEL, GRID) \
+    case lc_attn_code(FAMILY, DQ, ND, NW, PRE): hipLaunchKernelGGL(KERNEL, GRID, dim3(64 * NW), 0, lc_s(s), a); break
+    switch (route) {
+        LC_ATTN_CASE(LC_ATTN_SPLIT, 32, 1, 4, 1, (attn_h_kernel<32, 1, 4, true>), grid);     // training entry: measured pre-scales
+        LC_ATTN_CASE(LC_ATTN_SPLIT, 64, 1, 4, 1, (attn_h_kernel<64, 1, 4, true>), grid);
+        LC_ATTN_CASE(LC_ATTN_SPLIT, 32, 2, 4, 1, (attn_h_kernel<32, 2, 4, true>), grid);
+        LC_ATTN_CASE(LC_ATTN_SPLIT, 64, 2, 4, 1, (attn_h_kernel<64, 2, 4, true>), grid);
+        LC_ATTN_CASE(LC_ATTN_SPLIT, 32, 1, 8, 0, (attn_h_kernel<32, 1, 8>), grid8);
+        LC_ATTN_CASE(LC_ATTN_SPLIT, 64, 1, 8, 0, (attn_h_kernel<64, 1, 8>), grid8);
+        LC_ATTN_CASE(LC_ATTN_SPLIT, 32, 1, 4, 0, (attn_h_kernel<32, 1>), grid);
+        LC_ATTN_CASE(LC_ATTN_SPLIT, 64, 1, 4, 0, (attn_h_kernel<64, 1>), grid);
+        LC_ATTN_CASE(LC_ATTN_SPLIT, 32, 2, 4, 0, (attn_h_kernel<32, 2>), grid);
+        LC_ATTN_CASE(LC_ATTN_SPLIT, 64, 2, 4, 0, (attn_h_kernel<64, 2>), grid);
+        LC_ATTN_CASE(LC_ATTN_F32, 32, 1, 4, 0, (attn_kernel<32, 1>), grid);
+        LC_ATTN_CASE(LC_ATTN_F32, 64, 1, 4, 0, (attn_kernel<64, 1>), grid);
+        LC_ATTN_CASE(LC_ATTN_F32, 32, 2, 4, 0, (attn_kernel<32, 2>), grid);
+        LC_ATTN_CASE(LC_ATTN_F32, 64, 2, 4, 0, (attn_kernel<64, 2>), grid);
+        default: return LC_EUNSUP;
     }
-    if (dq == 32 && nd == 1) hipLaunchKernelGGL((attn_kernel<32, 1>), grid, dim3(256), 0, lc_s(s), a);
-    else if (dq == 64 && nd == 1) hipLaunchKernelGGL((attn_kernel<64, 1>), grid, dim3(256), 0, lc_s(s), a);
-    else if (dq == 32 && nd == 2) hipLaunchKernelGGL((attn_kernel<32, 2>), grid, dim3(256), 0, lc_s(s), a);
-    else hipLaunchKernelGGL((attn_kernel<64, 2>), grid, dim3(256), 0, lc_s(s), a);
+#undef LC_ATTN_CASE
     return lc_launch_status();
+}
+
+// (family, DQK, NDV, waves, PRE) of the kernel a forward call runs, packed as attention_route.h states; waves_env < 0:
+// this process's cached LC_ATTN_WAVES.  Pure host code: what the launcher above itself switches on.
+extern "C" int lc_attention_route(int split, int has_amax, int dqk, int dpos, int dv, int64_t bh, int Lq, int waves_env) {
+    return lc_attn_route_fwd(split, has_amax, dqk, dpos, dv, bh, Lq, waves_env < 0 ? attn_waves_env() : waves_env);
 }
 
 #define LC_ATTN_PARAMS                                                                            \
@@ -498,7 +504,8 @@ extern "C" int lc_attention_f16x2_fwd(LC_ATTN_PARAMS) { return attention_launch(
 extern "C" int lc_attention_train_fwd(const float* q, const float* k, const float* v, float* o, float* lse, int BH,
                                       int Lq, int Lk, int dqk, int dv, float scale, int f16x2, float* qkv_amax,
                                       lc_stream_t s) {
-    if (!q || !k || !v || !o || !lse || BH <= 0) return LC_EINVAL;
+    if (!q || !k || !v || !o || !lse || BH <= 0 || Lq <= 0 || Lk <= 0) return LC_EINVAL;
+    if (lc_attn_route_fwd(f16x2, qkv_amax != nullptr, dqk, 0, dv, BH, Lq, 0) < 0) return LC_EUNSUP;   // (before the memset below)
     unsigned* am = reinterpret_cast<unsigned*>(qkv_amax);
     if (am && f16x2) {
         if (hipMemsetAsync(am, 0, 3 * sizeof(unsigned), lc_s(s)) != hipSuccess) return lc_launch_status();

@@ -21,6 +21,7 @@
 //                        S = Q^T K, dV^T += dO P, dP = dO^T V, dK^T += Q dS
 #include "common.h"
 #include "f16x2.h"      // mfma_row
+#include "attention_route.h"
 
 namespace {
 
@@ -232,26 +233,31 @@ extern "C" int lc_attention_bwd(const float* q, const float* k, const float* v, 
                                 int Lk, int dqk, int dv_ch, float scale, lc_stream_t s) {
     if (!q || !k || !v || !o || !dout || !lse || !dsum_scratch || !dq || !dk || !dv || BH <= 0 || Lq <= 0 || Lk <= 0)
         return LC_EINVAL;
-    if (dqk <= 0 || dqk > 64 || dv_ch <= 0 || dv_ch > 64) return LC_EUNSUP;
+    const int route = lc_attn_route_bwd(0, dqk, dv_ch, BH);     // (B * heads > 65535: the grids' y extent)
+    if (route < 0) return route;
     AttnBwdArgs a;
     a.q = q; a.k = k; a.v = v; a.dout = dout; a.lse = lse; a.dsum = dsum_scratch;
     a.dq = dq; a.dk = dk; a.dv = dv;
     a.Lq = Lq; a.Lk = Lk; a.dqk = dqk; a.dv_ = dv_ch;
     a.scale = scale; a.qscale = scale * 1.4426950408889634f;
     hipLaunchKernelGGL(attn_dsum_kernel, dim3((Lq + 255) / 256, BH), dim3(256), 0, lc_s(s), o, dout, dsum_scratch, Lq, dv_ch);
-    const int dqp = dqk <= 32 ? 32 : 64, nd = dv_ch <= 32 ? 1 : 2;
     const dim3 gq((Lq + 127) / 128, BH), gk((Lk + 127) / 128, BH);
 #define LC_BWD(DQ, ND)                                                                         \
     do {                                                                                       \
         hipLaunchKernelGGL((attn_bwd_dq_kernel<DQ, ND>), gq, dim3(256), 0, lc_s(s), a);        \
         hipLaunchKernelGGL((attn_bwd_dkv_kernel<DQ, ND>), gk, dim3(256), 0, lc_s(s), a);       \
     } while (0)
-    if (dqp == 32 && nd == 1) LC_BWD(32, 1);
-    else if (dqp == 64 && nd == 1) LC_BWD(64, 1);
-    else if (dqp == 32 && nd == 2) LC_BWD(32, 2);
-    else LC_BWD(64, 2);
+    switch (route) {
+        case lc_attn_code(LC_ATTN_BWD_F32, 32, 1, 4, 0): LC_BWD(32, 1); break;
+        case lc_attn_code(LC_ATTN_BWD_F32, 64, 1, 4, 0): LC_BWD(64, 1); break;
+        case lc_attn_code(LC_ATTN_BWD_F32, 32, 2, 4, 0): LC_BWD(32, 2); break;
+        default: LC_BWD(64, 2); break;
+    }
 #undef LC_BWD
     return lc_launch_status();
 }
+
+// The kernel pair a backward call launches (split: lc_attention_bwd_f16x2), packed as attention_route.h states.  Pure host code.
+extern "C" int lc_attention_bwd_route(int split, int dqk, int dv_ch, int64_t bh) { return lc_attn_route_bwd(split, dqk, dv_ch, bh); }
 
 LC_TOUCH_TU(attention_bwd, attn_dsum_kernel)

@@ -19,6 +19,7 @@
 // it at 2^6, so dP, dS and the outputs carry that factor exactly until the epilogue divides it out.
 #include "common.h"
 #include "attention_split.h"      // P_PRE; the split: f16x2.h
+#include "attention_route.h"
 
 namespace {
 
@@ -345,7 +346,8 @@ extern "C" int lc_attention_bwd_f16x2(const float* q, const float* k, const floa
                                       int Lq, int Lk, int dqk, int dv_ch, float scale, const float* qkv_amax, lc_stream_t s) {
     if (!q || !k || !v || !o || !dout || !lse || !dsum_scratch || !dq || !dk || !dv || BH <= 0 || Lq <= 0 || Lk <= 0)
         return LC_EINVAL;
-    if (dqk <= 0 || dqk > 64 || dv_ch <= 0 || dv_ch > 64) return LC_EUNSUP;
+    const int route = lc_attn_route_bwd(1, dqk, dv_ch, BH);     // (B * heads > 65535: the grids' y extent)
+    if (route < 0) return route;
     AttnBwdHArgs a;
     unsigned* amax = reinterpret_cast<unsigned*>(dsum_scratch + (long long)BH * Lq);
     a.q = q; a.k = k; a.v = v; a.dout = dout; a.lse = lse; a.dsum = dsum_scratch; a.do_amax = amax;
@@ -356,17 +358,18 @@ extern "C" int lc_attention_bwd_f16x2(const float* q, const float* k, const floa
     if (hipMemsetAsync(amax, 0, sizeof(unsigned), lc_s(s)) != hipSuccess) return lc_launch_status();
     hipLaunchKernelGGL(attn_dsum_h_kernel, dim3((Lq + 255) / 256, BH), dim3(256), 0, lc_s(s), o, dout, dsum_scratch, amax, Lq,
                        dv_ch);
-    const int dqp = dqk <= 32 ? 32 : 64, nd = dv_ch <= 32 ? 1 : 2;
     const dim3 gq((Lq + 127) / 128, BH), gk((Lk + 127) / 128, BH);
 #define LC_BWD(DQ, ND)                                                                           \
     do {                                                                                         \
         hipLaunchKernelGGL((attn_bwd_dq_h_kernel<DQ, ND>), gq, dim3(256), 0, lc_s(s), a);        \
         hipLaunchKernelGGL((attn_bwd_dkv_h_kernel<DQ, ND>), gk, dim3(256), 0, lc_s(s), a);       \
     } while (0)
-    if (dqp == 32 && nd == 1) LC_BWD(32, 1);
-    else if (dqp == 64 && nd == 1) LC_BWD(64, 1);
-    else if (dqp == 32 && nd == 2) LC_BWD(32, 2);
-    else LC_BWD(64, 2);
+    switch (route) {
+        case lc_attn_code(LC_ATTN_BWD_SPLIT, 32, 1, 4, 0): LC_BWD(32, 1); break;
+        case lc_attn_code(LC_ATTN_BWD_SPLIT, 64, 1, 4, 0): LC_BWD(64, 1); break;
+        case lc_attn_code(LC_ATTN_BWD_SPLIT, 32, 2, 4, 0): LC_BWD(32, 2); break;
+        default: LC_BWD(64, 2); break;
+    }
 #undef LC_BWD
     return lc_launch_status();
 }

@@ -220,6 +220,7 @@ extern "C" int lc_attention_pack_units(const lc_cm_operand* src, void* kv, int B
                                        int cb0, int key0, int which, lc_stream_t s) {
     if (!src || !src->p || !kv || B <= 0 || heads <= 0 || L <= 0 || d <= 0 || cb0 < 0 || key0 < 0) return LC_EINVAL;
     if (Lk0 <= 0 || Lk0 % 32 || Lk1 < 0 || Lk1 > 32 || key0 % 32 || key0 + L > Lk0 + 32 * (Lk1 > 0)) return LC_EUNSUP;
+    if ((long long)B * heads > 65535) return LC_EUNSUP;      // the grids' z extent
     PackArgs a;
     a.src = *src; a.kv = (half8*)kv; a.heads = heads; a.L = L; a.tiles = Lk0 / 32 + (Lk1 > 0); a.d = d; a.cb0 = cb0; a.key0 = key0;
     if (which == 0) {
@@ -241,6 +242,7 @@ extern "C" int lc_attention_units_fwd(const lc_cm_operand* q, const lc_cm_operan
     if (!q || !q->p || !kv || !o || B <= 0 || heads <= 0 || Lq <= 0 || Lk0 <= 0 || Lk1 < 0 || dpos < 0) return LC_EINVAL;
     if (dpos > 0 && (!q_pos || !q_pos->p)) return LC_EINVAL;
     if (dqk <= 0 || dqk % 8 || dpos % 8 || dqk + dpos > 64 || dv <= 0 || dv > 32 || Lk0 % 32 || Lk1 > 32) return LC_EUNSUP;
+    if ((long long)B * heads > 65535) return LC_EUNSUP;      // the grid's y extent
     const lc_cm_operand none = {nullptr, 0, 0, 0};
     UArgs a;
     a.q = *q; a.qp = q_pos ? *q_pos : none; a.kv = (const half8*)kv;

@@ -1612,7 +1612,17 @@ def attention_cm(q, k, v, heads: int, scale: float, k2=None, v2=None, q_pos=None
     (views with arbitrary batch/channel strides, unit token stride).  Optional positional parts
     q_pos/k_pos/k2_pos [B, heads*dpos, L] are concatenated to each head's q/k channels inside the
     kernel; optional second key/value segment k2/v2 with Lk1 tokens (the 13 layout tokens of
-    ObjectAwareCrossAttention).  Batch stride 0 (expand) is allowed for step-invariant operands."""
+    ObjectAwareCrossAttention).  Batch stride 0 (expand) is allowed for step-invariant operands.
+
+    Range contract of precision "f16x2" (and of `attention_units` / `qkv_project_units`, which share its arithmetic): the
+    operands are split into fp16 halves after the CONSTANT pre-scale 16.  With m_q = max|q * scale * log2(e)|, m_k = max|k|,
+    m_v = max|v| (positional parts and the second segment included): while 0.25 <= m < 2048 (16 * m in [4, 32768)) for all
+    three, nothing saturates and the result is finite and no worse than 4 x the error of a float32 evaluation; the 2e-6
+    tolerance of the fp32 route holds where in addition m_q * m_k <= 32 / sqrt(dqk + dpos) (scores deviating by about one
+    nat; so m_q, m_k <= 128 / sqrt(dqk + dpos)), with m_v anywhere in its window
+    (tests/test_attention_matrix.py::test_range_window stands at every end).  Outside the window accuracy is lost or values
+    saturate without a report: use precision "f32" there.  A split request with dqk % 8 or dpos % 8 runs the fp32 kernels
+    (`lc_attention_route` reports the kernel of any call); B * heads <= 65535."""
     from ._lib import CmOperand
     import ctypes as C
 
