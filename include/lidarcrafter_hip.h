@@ -699,6 +699,30 @@ int lc_groupnorm_bwd_train(const float* x, int64_t x_bs, const float* dy, int64_
                            const float* shift, int64_t ss_bs, double* rows, float* dx, int64_t dx_bs,
                            float* dgamma, float* dbeta, float* dscale, float* dshift, int B, int C, int H, int W,
                            int G, int act_silu, float* amax_out, lc_stream_t s);
+/* Which way a backward call runs (pure host code, no GPU needed; the launchers and kernels switch on the same functions,
+ * csrc/conv_bwd_route.h and csrc/gn_bwd_route.h).  Addresses are passed modulo 16.
+ * lc_conv2d_ring_wgrad_route: split 0 = lc_conv2d_ring_wgrad, 1 = lc_conv2d_ring_wgrad_f16x2.  Fills
+ *   out[0] kernel family   1 exact-fp32 MFMA kernel, 2 f16x2-split kernel
+ *   out[1] staging         1 float4 loads, 0 scalar loads (fp32 kernel: W % 64, H W % 4, x_bs % 4, dy_bs % 4 or an address
+ *                          off 16 bytes; the split kernel has the float4 form only)
+ *   out[2] nsplit          blocks per 64 x 64 channel tile = partial sums per weight, from B H ceil(W / 64) pixel tiles
+ *   out[3] tiles           pixel tiles of the chosen kernel: B H ceil(W / 64) (fp32), B (H / 2) (W / 32) (split); blocks
+ *                          beyond the tile count write zero partials
+ *   out[4] bias branch     1 every (sample, channel) plane of dy is read as float4, 0 none is, 2 it differs by sample
+ *   out[5] bias offset     floats of the scratch in front of the Co * B fp64 bias partials (an even count);
+ *                          lc_conv2d_ring_wgrad_scratch_elems = out[5] + 2 Co B
+ *   out[6] scalar causes   fp32 kernel: bit 0 W % 64, 1 H W % 4, 2 x_bs % 4, 3 dy_bs % 4, 4 x address, 5 dy address
+ *   out[7] 0
+ *   and returns LC_OK, or the code of the entry where it refuses: LC_EINVAL for a size that is not positive, LC_EUNSUP for
+ *   ks other than 1 / 3 and, split = 1, for H odd, W % 32, a batch stride % 4 or an address off 16 bytes.
+ * lc_groupnorm_bwd_route: lc_groupnorm_bwd_train / lc_groupnorm_bwd.  Fills out[0] blocks per plane of the apply pass
+ *   (ceil(H W / 4096)), out[1] pixels per block, out[2] the apply pass's branch (1 float4, 0 scalar, 2 differs by sample:
+ *   float4 needs H W % 4 == 0, out[1] % 4 == 0 and the planes of x, dy and dx on 16 bytes), out[3] outer iterations of
+ *   the rows pass (4096 pixels each); LC_EINVAL for a size that is not positive or C % G. */
+int lc_conv2d_ring_wgrad_route(int split, int B, int Ci, int Co, int H, int W, int ks, int64_t x_bs, int64_t dy_bs,
+                               int x_addr_mod16, int dy_addr_mod16, int32_t* out /* [8] */);
+int lc_groupnorm_bwd_route(int B, int C, int H, int W, int G, int64_t x_bs, int64_t dy_bs, int64_t dx_bs,
+                           int x_addr_mod16, int dy_addr_mod16, int dx_addr_mod16, int32_t* out /* [4] */);
 
 /* ---------------------------------------------------------------------------------------------
  * Voxel scatter of the weight-free metrics (lidargen/metrics/metric_utils.py).

@@ -96,6 +96,8 @@ SIGNATURES = {
                                i32, i32, i32, vp]),
     "lc_groupnorm_bwd_train": (i32, [vp, i64, vp, i64, vp, vp, vp, vp, vp, i64, vp, vp, i64, vp, vp, vp, vp,
                                      i32, i32, i32, i32, i32, i32, vp, vp]),
+    "lc_conv2d_ring_wgrad_route": (i32, [i32, i32, i32, i32, i32, i32, i32, i64, i64, i32, i32, vp]),
+    "lc_groupnorm_bwd_route": (i32, [i32, i32, i32, i32, i32, i64, i64, i64, i32, i32, i32, vp]),
     "lc_resample2x_fwd": (i32, [vp, i64, vp, i64, i32, i32, i32, i32, i32, vp]),
     "lc_resample2x_stats_slots": (i64, [i32, i32, i32]),
     "lc_resample2x_stats_fwd": (i32, [vp, i64, vp, i64, i32, i32, i32, i32, i32, vp, vp]),

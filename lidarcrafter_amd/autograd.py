@@ -152,6 +152,13 @@ def _bs(t):
     return t.stride(0) if t.shape[0] > 1 else t.shape[1] * t.shape[2] * t.shape[3]
 
 
+def wgrad_split_accepts(H, W, x_bs, dy_bs, x_addr, dy_addr) -> bool:
+    """The shapes lc_conv2d_ring_wgrad_f16x2 takes (LC_EUNSUP otherwise): whole 2 x 32 pixel tiles and 16-byte aligned
+    rows.  tests/test_train_edges_host.py holds this against lc_conv2d_ring_wgrad_route on every row of its table."""
+    return (H % 2 == 0 and W % 32 == 0 and x_bs % 4 == 0 and dy_bs % 4 == 0 and
+            x_addr % 16 == 0 and dy_addr % 16 == 0)
+
+
 class ConvRing(torch.autograd.Function):
     """y = (conv_ring(x, W) + b [+ res]) * out_scale (3x3: W circular / H zero padding, 1x1: plain).  The residual add
     and the 1/sqrt(2) of a block's exit run in the conv's epilogue, as in the inference forward; the backward
@@ -195,8 +202,7 @@ class ConvRing(torch.autograd.Function):
         # the split weight gradient needs whole 2 x 32 pixel tiles and 16-byte aligned rows
         prec = ctx.prec
         w_split = (need_w and TRAIN_WGRAD_PRECISION == "f16x2" and prec == "f16x2" and
-                   H % 2 == 0 and W % 32 == 0 and _bs(x) % 4 == 0 and _bs(dy) % 4 == 0 and
-                   x.data_ptr() % 16 == 0 and dy.data_ptr() % 16 == 0)
+                   wgrad_split_accepts(H, W, _bs(x), _bs(dy), x.data_ptr(), dy.data_ptr()))
         if prec == "f16x2" and (ctx.needs_input_grad[0] or w_split):
             if dy_amax is not None:                             # one measurement serves dX and dW
                 K.range_from_amax(dy_amax[0], ctx.holder["bwd"], dy.device, dy_amax[1])

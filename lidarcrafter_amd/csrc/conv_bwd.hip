@@ -13,6 +13,7 @@
 // channel tile, each writing its partial sums, and a second kernel adds the partials in index
 // order (deterministic, no atomics).
 #include "common.h"
+#include "conv_bwd_route.h"
 #include "f16x2.h"
 
 namespace {
@@ -22,7 +23,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(const float* __restr
                                                            const float* __restrict__ dy, long long dy_bs,
                                                            float* __restrict__ part, int B, int Ci, int Co,
                                                            int H, int W, int ncib, int nsplit) {
-    constexpr int HALO = KS / 2, NTAP = KS * KS, TW = 64;
+    constexpr int HALO = KS / 2, NTAP = KS * KS, TW = LC_WGRAD_TW;
     constexpr int DS = TW + 1;                       // dY row stride (floats), odd
     constexpr int XC = TW + 2 * HALO;                // staged columns of X
     constexpr int XRS = XC | 1;                      // odd row stride
@@ -37,8 +38,8 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(const float* __restr
     const int cob = blockIdx.x / ncib, cib = blockIdx.x - cob * ncib;
     const int co0 = cob * 64, ci0 = cib * 64;
     const int split = blockIdx.y;
-    const int tiles_w = (W + TW - 1) / TW;
-    const int ntiles = B * H * tiles_w;
+    const int tiles_w = lc_wgrad_tiles_w(W);
+    const int ntiles = lc_wgrad_tiles(B, H, W);
     f32x16 acc[NTAP];
 #pragma unroll
     for (int t = 0; t < NTAP; ++t)
@@ -46,10 +47,9 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(const float* __restr
         for (int r = 0; r < 16; ++r) acc[t][r] = 0.0f;
     const int l31 = lane & 31, kk = lane >> 5;
     const long long HW = (long long)H * W;
-    // float4 staging when rows are 16-byte aligned and tiles are whole
-    const bool vec = (W % TW) == 0 && (HW & 3) == 0 && (x_bs & 3) == 0 && (dy_bs & 3) == 0 &&
-                     (reinterpret_cast<unsigned long long>(x) & 15) == 0 &&
-                     (reinterpret_cast<unsigned long long>(dy) & 15) == 0;
+    // float4 staging when rows are 16-byte aligned and tiles are whole (conv_bwd_route.h)
+    const bool vec = lc_wgrad_scalar_causes(W, HW, x_bs, dy_bs, (int)(reinterpret_cast<unsigned long long>(x) & 15),
+                                            (int)(reinterpret_cast<unsigned long long>(dy) & 15)) == 0;
     for (int tile = split; tile < ntiles; tile += nsplit) {
         const int tw = tile % tiles_w;
         const int h = (tile / tiles_w) % H, b = tile / (tiles_w * H);
@@ -177,7 +177,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_h_kernel(
     const float* __restrict__ x, long long x_bs, const float* __restrict__ dy, long long dy_bs,
     float* __restrict__ part, const lc_conv_range* __restrict__ rx, const lc_conv_range* __restrict__ rdy,
     int B, int Ci, int Co, int H, int W, int ncib, int nsplit) {
-    constexpr int HALO = KS / 2, NTAP = KS * KS, TR = 2, TWX = 32;
+    constexpr int HALO = KS / 2, NTAP = KS * KS, TR = LC_WGRAD_H_TR, TWX = LC_WGRAD_H_TW;
     constexpr int XR = TR + 2 * HALO;                  // staged X rows
     constexpr int XOFF = HALO ? 8 : 0;                 // halfs in front of column w0 (16-byte aligned interior)
     constexpr int RS = TWX + 2 * XOFF;                 // halfs per staged X row
@@ -193,7 +193,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_h_kernel(
     const int co0 = cob * 64, ci0 = cib * 64;
     const int split = blockIdx.y;
     const int tiles_w = W / TWX, tiles_h = H / TR;
-    const int ntiles = B * tiles_h * tiles_w;
+    const int ntiles = lc_wgrad_h_tiles(B, H, W);
     const float sx = rx->x_scale, sdy = rdy->x_scale;
     f32x16 acc[NTAP];
 #pragma unroll
@@ -367,7 +367,7 @@ __global__ __launch_bounds__(256) void bias_grad_plane_kernel(const float* __res
     const int co = blockIdx.x, b = blockIdx.y;
     const float* p = dy + b * dy_bs + (long long)co * HW;
     float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-    if ((HW & 3) == 0 && (reinterpret_cast<unsigned long long>(p) & 15) == 0) {
+    if (lc_bias_grad_vec(HW, (int)(reinterpret_cast<unsigned long long>(p) & 15))) {
         const f32x4* p4 = reinterpret_cast<const f32x4*>(p);
         for (long long i = threadIdx.x; i < (HW >> 2); i += 256) {
             const f32x4 v = p4[i];
@@ -392,23 +392,12 @@ __global__ void bias_grad_fold_kernel(const double* __restrict__ part, float* __
     db[co] = accumulate ? db[co] + (float)s : (float)s;
 }
 
-int wgrad_splits(int B, int Ci, int Co, int H, int W) {
-    const int tiles = B * H * ((W + 63) / 64);
-    const int ctiles = ((Co + 63) / 64) * ((Ci + 63) / 64);
-    int n = (512 + ctiles - 1) / ctiles;              // one full wave of blocks (2 resident per CU): equal
-                                                      // work per block, and half the partials to reduce
-    if (n > tiles) n = tiles;
-    if (n < 1) n = 1;
-    return n;
-}
-
 }  // namespace
 
 extern "C" int64_t lc_conv2d_ring_wgrad_scratch_elems(int B, int Ci, int Co, int H, int W, int ks) {
     if (B <= 0 || Ci <= 0 || Co <= 0 || H <= 0 || W <= 0 || (ks != 1 && ks != 3)) return 0;
     // weight partials (rounded up to an even count) + Co * B fp64 bias partials
-    const int64_t wp = (int64_t)wgrad_splits(B, Ci, Co, H, W) * Co * Ci * ks * ks;
-    return ((wp + 1) & ~(int64_t)1) + 2 * (int64_t)Co * B;
+    return lc_wgrad_scratch_elems(lc_wgrad_splits(B, Ci, Co, H, W), B, Ci, Co, ks);
 }
 
 extern "C" int lc_conv2d_ring_wgrad(const float* x, int64_t x_bs, const float* dy, int64_t dy_bs,
@@ -418,7 +407,7 @@ extern "C" int lc_conv2d_ring_wgrad(const float* x, int64_t x_bs, const float* d
         return LC_EINVAL;
     if (ks != 1 && ks != 3) return LC_EUNSUP;
     const int ncib = (Ci + 63) / 64, ncob = (Co + 63) / 64;
-    const int nsplit = wgrad_splits(B, Ci, Co, H, W);
+    const int nsplit = lc_wgrad_splits(B, Ci, Co, H, W);
     dim3 grid(ncob * ncib, nsplit);
     if (ks == 3)
         hipLaunchKernelGGL(conv_wgrad_kernel<3>, grid, dim3(256), 0, lc_s(s), x, (long long)x_bs, dy,
@@ -430,8 +419,7 @@ extern "C" int lc_conv2d_ring_wgrad(const float* x, int64_t x_bs, const float* d
     hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, lc_s(s),
                        scratch, n, nsplit, dw, accumulate);
     if (dbias) {
-        const long long wp = ((long long)nsplit * n + 1) & ~1LL;
-        double* bpart = reinterpret_cast<double*>(scratch + wp);
+        double* bpart = reinterpret_cast<double*>(scratch + lc_wgrad_bias_offset(nsplit, Ci, Co, ks));
         hipLaunchKernelGGL(bias_grad_plane_kernel, dim3(Co, B), dim3(256), 0, lc_s(s), dy, (long long)dy_bs,
                            bpart, B, (long long)H * W);
         hipLaunchKernelGGL(bias_grad_fold_kernel, dim3((Co + 255) / 256), dim3(256), 0, lc_s(s), bpart, dbias,
@@ -448,11 +436,11 @@ extern "C" int lc_conv2d_ring_wgrad_f16x2(const float* x, int64_t x_bs, const fl
         return LC_EINVAL;
     if (ks != 1 && ks != 3) return LC_EUNSUP;
     // whole 2 x 32 tiles, 16-byte aligned rows (anything else: lc_conv2d_ring_wgrad)
-    if ((H & 1) || (W & 31) || (x_bs & 3) || (dy_bs & 3) || (reinterpret_cast<uintptr_t>(x) & 15) ||
-        (reinterpret_cast<uintptr_t>(dy) & 15))
+    if (lc_wgrad_h_unsupported(H, W, x_bs, dy_bs, (int)(reinterpret_cast<uintptr_t>(x) & 15),
+                               (int)(reinterpret_cast<uintptr_t>(dy) & 15)))
         return LC_EUNSUP;
     const int ncib = (Ci + 63) / 64, ncob = (Co + 63) / 64;
-    const int nsplit = wgrad_splits(B, Ci, Co, H, W);
+    const int nsplit = lc_wgrad_splits(B, Ci, Co, H, W);
     dim3 grid(ncob * ncib, nsplit);
     if (ks == 3)
         hipLaunchKernelGGL(conv_wgrad_h_kernel<3>, grid, dim3(256), 0, lc_s(s), x, (long long)x_bs, dy,
@@ -464,14 +452,18 @@ extern "C" int lc_conv2d_ring_wgrad_f16x2(const float* x, int64_t x_bs, const fl
     hipLaunchKernelGGL(wgrad_fold_h_kernel, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, lc_s(s), scratch, n,
                        nsplit, dw, Co, Ci, ks * ks, x_range, dy_range, accumulate);
     if (dbias) {
-        const long long wp = ((long long)nsplit * n + 1) & ~1LL;
-        double* bpart = reinterpret_cast<double*>(scratch + wp);
+        double* bpart = reinterpret_cast<double*>(scratch + lc_wgrad_bias_offset(nsplit, Ci, Co, ks));
         hipLaunchKernelGGL(bias_grad_plane_kernel, dim3(Co, B), dim3(256), 0, lc_s(s), dy, (long long)dy_bs,
                            bpart, B, (long long)H * W);
         hipLaunchKernelGGL(bias_grad_fold_kernel, dim3((Co + 255) / 256), dim3(256), 0, lc_s(s), bpart, dbias,
                            Co, B, accumulate);
     }
     return lc_launch_status();
+}
+
+extern "C" int lc_conv2d_ring_wgrad_route(int split, int B, int Ci, int Co, int H, int W, int ks, int64_t x_bs,
+                                          int64_t dy_bs, int x_addr_mod16, int dy_addr_mod16, int32_t* out) {
+    return lc_wgrad_route(split, B, Ci, Co, H, W, ks, x_bs, dy_bs, x_addr_mod16, dy_addr_mod16, out);
 }
 
 LC_TOUCH_TU(conv_bwd, conv_wgrad_kernel<3>)

@@ -5,6 +5,7 @@
 // apply reads once and writes once.  A group is a contiguous span of (C/G)*H*W floats in NCHW.
 #include "common.h"
 #include "f16x2.h"
+#include "gn_bwd_route.h"
 #include "stats_entry.h"
 
 namespace {
@@ -239,9 +240,9 @@ __global__ __launch_bounds__(256) void gn_bwd_rows_kernel(
     const float* xp = x + b * x_bs + (long long)c * HW;
     const float* dp = dy + b * dy_bs + (long long)c * HW;
     double r1 = 0.0, r3 = 0.0;
-    for (long long i0 = threadIdx.x; i0 < HW; i0 += 256 * 16) {
+    for (long long i0 = threadIdx.x; i0 < HW; i0 += LC_GN_BWD_SLAB) {
         float a1 = 0.f, a3 = 0.f;                              // fp32 over <= 16 values, then fp64
-        for (long long i = i0; i < HW && i < i0 + 256 * 16; i += 256) {
+        for (long long i = i0; i < HW && i < i0 + LC_GN_BWD_SLAB; i += 256) {
             const float xh = (xp[i] - mu) * rstd;
             float d = dp[i];
             if (act) d *= silu_grad((xh * ga + be) * sc + sf);
@@ -306,7 +307,7 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(
     const float* xp = x + b * x_bs + (long long)c * HW;
     const float* dp = dy + b * dy_bs + (long long)c * HW;
     float* op = dx + b * dx_bs + (long long)c * HW;
-    const long long per = (HW + gridDim.x - 1) / gridDim.x;
+    const long long per = lc_gn_bwd_per(HW, (int)gridDim.x);
     const long long lo = blockIdx.x * per, hi = lo + per < HW ? lo + per : HW;
     float am = 0.0f;
     const auto g1 = [&](float xv, float d) {
@@ -316,8 +317,8 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(
         am = fmaxf(am, fabsf(r));
         return r;
     };
-    if ((HW & 3) == 0 && (per & 3) == 0 && ((reinterpret_cast<uintptr_t>(xp) | reinterpret_cast<uintptr_t>(dp) |
-                                             reinterpret_cast<uintptr_t>(op)) & 15) == 0) {
+    if (lc_gn_bwd_vec(HW, per, (int)(reinterpret_cast<uintptr_t>(xp) & 15), (int)(reinterpret_cast<uintptr_t>(dp) & 15),
+                      (int)(reinterpret_cast<uintptr_t>(op) & 15))) {
         for (long long i = lo + threadIdx.x * 4; i < hi; i += 1024) {
             const f32x4 xv = *reinterpret_cast<const f32x4*>(xp + i), dv = *reinterpret_cast<const f32x4*>(dp + i);
             f32x4 r;
@@ -548,9 +549,11 @@ inline void gn_apply_grid(int B, int C, int G, long long HW, int* slabs, int* cp
 // partial maximum per block of their apply pass
 extern "C" int64_t lc_groupnorm_amax_partials(int B, int C, int H, int W, int G, int backward) {
     if (B <= 0 || C <= 0 || G <= 0 || C % G || H <= 0 || W <= 0) return 0;
+    // backward: one per block of gn_bwd_apply_kernel, whose slab count is the launcher's (gn_bwd_route.h)
+    if (backward) return (int64_t)lc_gn_bwd_slabs((long long)H * W) * C * B;
     int slabs, cpb;
     gn_apply_grid(B, C, G, (long long)H * W, &slabs, &cpb);
-    return (int64_t)slabs * (backward ? C : C / cpb) * B;
+    return (int64_t)slabs * (C / cpb) * B;
 }
 
 extern "C" int lc_groupnorm_apply_train(const float* x, int64_t x_bs, const double* partials,
@@ -724,13 +727,12 @@ extern "C" int lc_groupnorm_bwd_train(const float* x, int64_t x_bs, const float*
                                       float* dx, int64_t dx_bs, float* dgamma, float* dbeta, float* dscale,
                                       float* dshift, int B, int C, int H, int W, int G, int act_silu,
                                       float* amax_out, lc_stream_t s) {
-    if (!x || !dy || !mean_rstd || !rows || !dx || B <= 0 || G <= 0 || C % G) return LC_EINVAL;
+    if (!x || !dy || !mean_rstd || !rows || !dx || B <= 0 || C <= 0 || H <= 0 || W <= 0 || G <= 0 || C % G) return LC_EINVAL;
     const long long HW = (long long)H * W;
     hipLaunchKernelGGL(gn_bwd_rows_kernel, dim3(C, B), dim3(256), 0, lc_s(s), x, (long long)x_bs, dy,
                        (long long)dy_bs, mean_rstd, gamma, beta, scale, shift, (long long)ss_bs, rows, C,
                        G, HW, act_silu);
-    int slabs = (int)((HW + 4095) / 4096);
-    if (slabs < 1) slabs = 1;
+    const int slabs = lc_gn_bwd_slabs(HW);
     hipLaunchKernelGGL(gn_bwd_apply_kernel, dim3(slabs, C, B), dim3(256), 0, lc_s(s), x, (long long)x_bs,
                        dy, (long long)dy_bs, mean_rstd, gamma, beta, scale, shift, (long long)ss_bs, rows,
                        dx, (long long)dx_bs, C, G, HW, act_silu, dgamma, dbeta, dscale, dshift, B, amax_out);
@@ -744,6 +746,11 @@ extern "C" int lc_groupnorm_bwd(const float* x, int64_t x_bs, const float* dy, i
                                 int act_silu, lc_stream_t s) {
     return lc_groupnorm_bwd_train(x, x_bs, dy, dy_bs, mean_rstd, gamma, beta, scale, shift, ss_bs, rows, dx, dx_bs,
                                   nullptr, nullptr, nullptr, nullptr, B, C, H, W, G, act_silu, nullptr, s);
+}
+
+extern "C" int lc_groupnorm_bwd_route(int B, int C, int H, int W, int G, int64_t x_bs, int64_t dy_bs, int64_t dx_bs,
+                                      int x_addr_mod16, int dy_addr_mod16, int dx_addr_mod16, int32_t* out) {
+    return lc_gn_bwd_route(B, C, H, W, G, x_bs, dy_bs, dx_bs, x_addr_mod16, dy_addr_mod16, dx_addr_mod16, out);
 }
 
 LC_TOUCH_TU(norm, gn_stats_kernel)
