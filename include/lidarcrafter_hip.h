@@ -1097,6 +1097,48 @@ int lc_rangenet_conv_fwd(const float* x, const float* wpk, const float* bias, co
                          int B, int Ci, int Co, int H, int W, int mode, int act, lc_stream_t s);
 int lc_rangenet_reduce_fwd(const float* x, float* out, int B, int C, int H, int W, int kind, lc_stream_t s);
 
+/* ---------------------------------------------------------------------------------------------
+ * PointMLP object extractor (csrc/pointmlp.hip): farthest point sampling, k nearest neighbours, the
+ * grouped and normalised operand of a stage, dense layers on [B, C, L] and the maximum over groups of columns.  Contiguous
+ * float32 / int32 tensors; no atomics, every reduction in a fixed order, a cloud's bits do not depend on the batch it is
+ * in; every entry checks its arguments before any launch.
+ *   lc_fps_fwd: xyz [B,N,3] (finite) -> idx [B,M], the greedy farthest-point sequence from index 0: running distances
+ *     start at 1e10, d = (dx dx + dy dy) + dz dz in float32 with separately rounded operations, among equal maxima the
+ *     smallest (rev(k mod bs), k) wins, bs = the largest power of two <= min(N, 1024) and rev the bit reversal over log2 bs
+ *     bits (the reference kernel's strided scan and reduction tree).  M may exceed the number of distinct points (index 0
+ *     repeats).  N <= LC_FPS_MAX_N (LC_EUNSUP above).
+ *   lc_knn_fwd: query_idx [B,S] indexes xyz [B,N,3]; out [B,S,K] = the K points nearest to each query, the same distance
+ *     expression, ascending (distance, index).  1 <= K <= min(N, LC_KNN_MAX_K) (K > N: LC_EINVAL), N <= LC_KNN_MAX_N,
+ *     B <= 65535.  A query index outside [0, N) gives a row of -1.
+ *   lc_pointmlp_group_fwd: x [B,d,N], fps_idx [B,S], knn_idx [B,S,K] (indices are clamped into [0, N)) ->
+ *     out [B,2d,S K]: out[b,c,sK+k] = alpha[c] (x[b,c,knn] - x[b,c,fps[s]]) / (sigma_b + 1e-5) + beta[c],
+ *     out[b,d+c,sK+k] = x[b,c,fps[s]]; sigma_b the UNBIASED standard deviation over all S K d differences of cloud b (float64
+ *     two-level sum; sigma [B] receives it when not NULL).  scratch: lc_pointmlp_group_scratch_elems(B,S,K) doubles, written
+ *     before they are read by the same call.  S K d >= 2 (LC_EINVAL).
+ *   lc_pointmlp_conv_fwd: y [B,Co,L] = act(W x + bias (+ res)), x [B,Ci,L], res [B,Co,L] or NULL added BEFORE the
+ *     activation, act 1 = ReLU, 0 = none.  Exact fp32 on the f32-input MFMA; k order: input channels in chunks of 32
+ *     ascending, every chunk an fma chain from zero, the chunks added in ascending order.  wpk: the device copy of
+ *     lc_pointmlp_pack_weight (HOST memory: w [Co,Ci] -> lc_pointmlp_packed_weight_elems(Ci,Co) floats, zero-filled past Ci and
+ *     Co; any positive widths), 16-byte aligned (LC_EUNSUP).  y may not alias x or res (LC_EINVAL).
+ *   lc_pointmlp_groupmax_fwd: x [B,C,G K] -> out[b out_bs + c out_cs + g out_gs] = max over k of x[b,c,gK+k].
+ *   lc_pointmlp_limit(i): 0 LC_FPS_MAX_N, 1 LC_KNN_MAX_N, 2 LC_KNN_MAX_K, 3 channels per chunk, 4 output channels per wave,
+ *     5 columns per wave, 6 columns per grouping block. */
+#define LC_FPS_MAX_N 8192
+#define LC_KNN_MAX_N 8192
+#define LC_KNN_MAX_K 32
+int lc_pointmlp_limit(int which);
+int lc_fps_fwd(const float* xyz, int* idx, int B, int N, int M, lc_stream_t s);
+int lc_knn_fwd(const float* xyz, const int* query_idx, int* out, int B, int N, int S, int K, lc_stream_t s);
+int64_t lc_pointmlp_group_scratch_elems(int B, int S, int K);
+int lc_pointmlp_group_fwd(const float* x, const int* fps_idx, const int* knn_idx, const float* alpha, const float* beta,
+                          float* out, double* scratch, float* sigma, int B, int d, int N, int S, int K, lc_stream_t s);
+int64_t lc_pointmlp_packed_weight_elems(int Ci, int Co);
+int lc_pointmlp_pack_weight(const float* w, int Ci, int Co, float* out);
+int lc_pointmlp_conv_fwd(const float* x, const float* wpk, const float* bias, const float* res, float* y, int B, int Ci,
+                         int Co, int L, int act, lc_stream_t s);
+int lc_pointmlp_groupmax_fwd(const float* x, float* out, int B, int C, int G, int K, int64_t out_bs, int64_t out_cs,
+                             int64_t out_gs, lc_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

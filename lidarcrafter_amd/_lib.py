@@ -215,6 +215,15 @@ SIGNATURES = {
     "lc_rangenet_pack_weight": (i32, [vp, i32, i32, i32, vp]),
     "lc_rangenet_conv_fwd": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
     "lc_rangenet_reduce_fwd": (i32, [vp, vp, i32, i32, i32, i32, i32, vp]),
+    "lc_pointmlp_limit": (i32, [i32]),
+    "lc_fps_fwd": (i32, [vp, vp, i32, i32, i32, vp]),
+    "lc_knn_fwd": (i32, [vp, vp, vp, i32, i32, i32, i32, vp]),
+    "lc_pointmlp_group_scratch_elems": (i64, [i32, i32, i32]),
+    "lc_pointmlp_group_fwd": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
+    "lc_pointmlp_packed_weight_elems": (i64, [i32, i32]),
+    "lc_pointmlp_pack_weight": (i32, [vp, i32, i32, vp]),
+    "lc_pointmlp_conv_fwd": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
+    "lc_pointmlp_groupmax_fwd": (i32, [vp, vp, i32, i32, i32, i32, i64, i64, i64, vp]),
 }
 
 _lib = None

@@ -4,7 +4,10 @@ Distance (`models.minkowskinet`, `metric_utils.compute_logits`, `eval_utils.comp
 csrc/spconv.hip) and the Frechet Point-Voxel Distance (`models.spvcnn`, `metric_utils.compute_point_voxel_logits`,
 `eval_utils.compute_fpvd`; point <-> voxel exchanges in csrc/spvoxel.hip) and the Frechet Range Image Distance
 (`models.rangenet`, `metric_utils.compute_range_logits`, `eval_utils.compute_frid`; dense convolutions in
-csrc/rangenet.hip), with its sibling FRD of the reference's own evaluator (`extractor.rangenet`, `eval_utils.compute_frd`)."""
+csrc/rangenet.hip), with its sibling FRD of the reference's own evaluator (`extractor.rangenet`, `eval_utils.compute_frd`),
+and the object half: the PointMLP extractor (`extractor.pointmlp`; farthest point sampling, k nearest neighbours and grouped
+dense layers in csrc/pointmlp.hip), `datasets.nuscenes_object_dataset.NuscObject`, `fg_object` and
+`eval_utils.compute_obj_scores`."""
 import os
 
 # a score line as the reference prints it: a 50-column rule above and below `|<16 blanks>NAME:1.2345E+00<17 blanks>|`

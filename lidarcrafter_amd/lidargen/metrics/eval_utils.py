@@ -211,3 +211,21 @@ def compute_frd(reference, samples, model, preprocess=None, batch_size=16, colum
     score = distribution.compute_frechet_distance(feats[0], feats[1])
     print(OUTPUT_TEMPLATE.format("FRD ", score))
     return score
+
+
+def compute_obj_scores(real_set, gen_set, class_name="car"):
+    """The evaluator's 'obj' block (tools/evaluation/evaluate_our.py:424-439) on two object sets of
+    `fg_object.get_fg_object_set_feature`: {'frechet_distance', 'squared_mmd'} of the PointMLP features and {'jsd', 'mmd'} of
+    the object BEV histograms of `class_name`.  One score line per number."""
+    from . import bev
+
+    real, gen = real_set[class_name], gen_set[class_name]
+    dev = "cuda" if torch.cuda.is_available() else "cpu"
+    hists = [torch.from_numpy(np.asarray(s["bev_hists"])).to(dev).float() for s in (real, gen)]
+    out = {"frechet_distance": float(distribution.compute_frechet_distance(real["pts_feat"], gen["pts_feat"])),
+           "squared_mmd": float(distribution.compute_squared_mmd(real["pts_feat"], gen["pts_feat"])),
+           "jsd": float(bev.compute_jsd_2d(*hists)),
+           "mmd": float(bev.compute_mmd_2d(*hists))}
+    for name, key in (("OFD ", "frechet_distance"), ("OMMD", "squared_mmd"), ("OJSD", "jsd"), ("OBMD", "mmd")):
+        print(OUTPUT_TEMPLATE.format(name, out[key]))
+    return out

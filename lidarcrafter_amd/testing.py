@@ -415,3 +415,31 @@ def rangenet_images(B: int, H: int, W: int, seed: int, holes: float = 0.15) -> t
                      depth * torch.sin(pitch).expand(1, 1, H, W), torch.rand((B, 1, H, W), generator=g)], dim=1)
     hole = torch.rand((B, 1, H, W), generator=g) < holes
     return torch.where(hole, torch.full_like(img, -1.0), img).contiguous()
+
+
+@torch.no_grad()
+def seeded_fill_pointmlp(module: torch.nn.Module, salt: int = 0) -> torch.nn.Module:
+    """Seeded weights for a PointMLP `Model` of either module tree, keyed by state_dict name: conv / linear weights
+    N(0, 2 / fan_in) (0.5 of that on the second layer of every residual block, whose output is added to the block's input),
+    biases 0.1 N, BatchNorm gains in U(0.5, 1.5), BatchNorm biases and running means 0.2 N, running variances in
+    U(0.5, 1.5), affine_alpha in U(0.5, 1.5) and affine_beta 0.2 N: nothing is left at its initial value."""
+    bn_names = {n for n, m in module.named_modules() if isinstance(m, torch.nn.BatchNorm1d)}
+    for key, p in list(module.named_parameters()) + list(module.named_buffers()):
+        if key.endswith("num_batches_tracked"):
+            continue
+        g = _gen_for(key, salt)
+        owner, leaf = key.rsplit(".", 1) if "." in key else ("", key)
+        if leaf == "affine_alpha":
+            v = 0.5 + torch.rand(p.shape, generator=g)
+        elif leaf == "affine_beta":
+            v = 0.2 * torch.randn(p.shape, generator=g)
+        elif owner in bn_names:
+            v = 0.5 + torch.rand(p.shape, generator=g) if leaf in ("weight", "running_var") else \
+                0.2 * torch.randn(p.shape, generator=g)
+        elif leaf == "weight":
+            fan_in = max(1, p.numel() // p.shape[0])
+            v = torch.randn(p.shape, generator=g) * ((0.5 if ".net2." in key else 2.0) / fan_in) ** 0.5
+        else:
+            v = 0.1 * torch.randn(p.shape, generator=g)
+        p.copy_(v.to(device=p.device, dtype=p.dtype))
+    return module
