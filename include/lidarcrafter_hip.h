@@ -1139,6 +1139,41 @@ int lc_pointmlp_conv_fwd(const float* x, const float* wpk, const float* bias, co
 int lc_pointmlp_groupmax_fwd(const float* x, float* out, int B, int C, int G, int K, int64_t out_bs, int64_t out_cs,
                              int64_t out_gs, lc_stream_t s);
 
+/* ---------------------------------------------------------------------------------------------
+ * Radius-limited nearest neighbour and point-to-point ICP on a ragged batch of float64 clouds (csrc/icp.hip, DESIGN.md
+ * section 5p): the registration of the temporal metric TTCE (lidargen/metrics/temporal.py estimate_transform_icp, i.e.
+ * Open3D registration_icp with TransformationEstimationPointToPoint and default criteria, restated).
+ * Operands: points [total,3] float64 (finite), offsets [C+1] int32 (cloud c owns rows offsets[c] ... offsets[c+1]-1), pairs
+ * [P,2] int32 (source cloud, target cloud), T [P,4,4] float64 row-major -- all DEVICE memory; max_cloud / max_src: an upper
+ * bound of the largest cloud / the largest source cloud (it sizes the launches; a larger cloud is not registered).
+ * Offsets or pair entries that do not describe rows of `points` make an empty cloud, never an access outside the operands.
+ *   lc_nn_grid_build: the search structure of EVERY cloud, once: a grid of cubic cells over the cloud's bounding box, edge h0
+ *     doubled until the grid has at most 2^20 cells (histogram, exclusive scan, scatter).  grid: lc_nn_grid_bytes(C, total)
+ *     bytes, 16-byte aligned (0: C > 65535 or total beyond 32-bit element offsets).  Any h0 > 0 gives the same results.
+ *   lc_nn_radius: one correspondence pass.  For source point i of pair p: q = T[p] points[i] (float64, no contraction),
+ *     idx[p*max_src+i] = the target point of the smallest d2 = (dx dx + dy dy) + dz dz among those with d2 <= radius^2, the
+ *     SMALLEST index among equal minima (whatever the order inside a cell), -1 if none; d2[p*max_src+i] that distance (+inf
+ *     if none).  Entries past a pair's source size are not written.
+ *   lc_icp_run: T (in: the initial transforms, out: the result) <- the ICP loop: pass; for i < max_iteration { update =
+ *     the rigid least-squares fit of the current correspondences (Umeyama without scale; computed as Horn's quaternion, the
+ *     same optimum; identity without correspondences); T = update T; pass; stop when |d fitness| < relative_fitness and
+ *     |d rmse| < relative_rmse }.  fitness [P] = correspondences / source points, inlier_rmse [P] = sqrt(sum d2 /
+ *     correspondences) (0 without), iterations [P] = updates applied.  T is always applied to the original source points.
+ *     2 max_iteration + 3 launches, no host synchronisation; the kernels of a finished pair return at once.  Sums are
+ *     float64 partials per 256-point block added in block order: no float atomics, the bits of a pair are the same in every
+ *     run and in every batch.  scratch: lc_icp_scratch_bytes(P, max_src) bytes, 16-byte aligned, initialised by the call.
+ * P <= 65535 and C <= 65535 (LC_EUNSUP above, before any launch); null pointers, sizes < 1, radius or h0 not positive and
+ * finite: LC_EINVAL. */
+int64_t lc_nn_grid_bytes(int C, int64_t total);
+int lc_nn_grid_build(const double* points, const int32_t* offsets, int C, int64_t total, int max_cloud, double h0, void* grid,
+                     lc_stream_t s);
+int lc_nn_radius(const double* points, const int32_t* offsets, int C, int64_t total, const void* grid, const int32_t* pairs,
+                 const double* T, int P, int max_src, double radius, int32_t* idx, double* d2, lc_stream_t s);
+int64_t lc_icp_scratch_bytes(int P, int max_src);
+int lc_icp_run(const double* points, const int32_t* offsets, int C, int64_t total, const void* grid, const int32_t* pairs,
+               int P, int max_src, double radius, int max_iteration, double relative_fitness, double relative_rmse, double* T,
+               double* fitness, double* inlier_rmse, int32_t* iterations, void* scratch, lc_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -224,6 +224,11 @@ SIGNATURES = {
     "lc_pointmlp_pack_weight": (i32, [vp, i32, i32, vp]),
     "lc_pointmlp_conv_fwd": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
     "lc_pointmlp_groupmax_fwd": (i32, [vp, vp, i32, i32, i32, i32, i64, i64, i64, vp]),
+    "lc_nn_grid_bytes": (i64, [i32, i64]),
+    "lc_nn_grid_build": (i32, [vp, vp, i32, i64, i32, f64, vp, vp]),
+    "lc_nn_radius": (i32, [vp, vp, i32, i64, vp, vp, vp, i32, i32, f64, vp, vp, vp]),
+    "lc_icp_scratch_bytes": (i64, [i32, i32]),
+    "lc_icp_run": (i32, [vp, vp, i32, i64, vp, vp, i32, i32, f64, i32, f64, f64, vp, vp, vp, vp, vp, vp]),
 }
 
 _lib = None

@@ -2772,6 +2772,131 @@ def emd_forward(xyz1: torch.Tensor, xyz2: torch.Tensor, eps: float, iters: int, 
     return dist, assignment
 
 
+# Cell edge of the nearest-neighbour grid as a fraction of the search radius (devtools/ttce_time.py sweeps it,
+# profiles/temporal_metrics.txt); any positive value gives the same results.
+NN_CELL_RATIO = 0.25
+
+
+class NNGrid:
+    """The cell grids of every cloud of a ragged batch (lc_nn_grid_build), with the operands they were built from."""
+    __slots__ = ("points", "offsets", "sizes", "buf", "C", "total")
+
+
+def _req_f64(t: torch.Tensor, name: str) -> None:
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise RuntimeError(f"lidarcrafter_amd.ops: `{name}` must be a CUDA(HIP) tensor -- the hot "
+                           "path has no CPU fallback (oracle/ holds the CPU restatement for tests)")
+    if t.dtype != torch.float64:
+        raise TypeError(f"`{name}` must be float64, got {t.dtype}")
+
+
+def nn_grid(points: torch.Tensor, offsets, radius: float, cell_ratio: Optional[float] = None) -> NNGrid:
+    """points [total,3] float64 CUDA, offsets [C+1] (cloud c = rows offsets[c]:offsets[c+1]) -> the search structure of
+    every cloud for nn_radius / icp_point_to_point at about this radius: cubic cells of edge radius * cell_ratio, doubled
+    per cloud until its grid fits 2^20 cells.  Non-finite coordinates raise ValueError (their cell is undefined)."""
+    _req_f64(points, "points")
+    if points.dim() != 2 or points.shape[1] != 3 or points.shape[0] < 1:
+        raise ValueError("nn_grid: points must be [total,3] with total >= 1")
+    off = torch.as_tensor(offsets).detach().to("cpu", torch.int64).reshape(-1)
+    C = off.numel() - 1
+    total = points.shape[0]
+    if C < 1 or int(off[0]) != 0 or int(off[-1]) != total or bool((off[1:] < off[:-1]).any()):
+        raise ValueError("nn_grid: offsets must rise from 0 to len(points)")
+    ratio = NN_CELL_RATIO if cell_ratio is None else float(cell_ratio)
+    if not (float(radius) > 0.0 and ratio > 0.0) or float(radius) * ratio == float("inf"):
+        raise ValueError("nn_grid: radius and cell_ratio must be positive and finite")
+    points = points.contiguous()
+    if not bool(torch.isfinite(points).all()):
+        raise ValueError("nn_grid: non-finite coordinates")
+    g = NNGrid()
+    g.points, g.C, g.total = points, C, total
+    g.sizes = (off[1:] - off[:-1]).tolist()
+    g.offsets = off.to(torch.int32).to(points.device)
+    nbytes = int(lib().lc_nn_grid_bytes(C, total))
+    if nbytes <= 0:
+        raise ValueError("nn_grid: more clouds or points than lc_nn_grid_build takes")
+    g.buf = torch.empty(nbytes, device=points.device, dtype=torch.uint8)
+    check(lib().lc_nn_grid_build(points.data_ptr(), g.offsets.data_ptr(), C, total, max(max(g.sizes), 1),
+                                 float(radius) * ratio, g.buf.data_ptr(), _stream()), "lc_nn_grid_build")
+    return g
+
+
+def _nn_operands(fn, points, offsets, pairs, radius, grid):
+    if grid is None:
+        grid = nn_grid(points, offsets, radius)
+    elif not isinstance(points, torch.Tensor) or points.data_ptr() != grid.points.data_ptr() \
+            or points.shape[0] != grid.total:
+        raise ValueError(f"{fn}: `grid` was built from other points")
+    pr = torch.as_tensor(pairs).detach().to("cpu", torch.int64).reshape(-1, 2)
+    if pr.shape[0] and (int(pr.min()) < 0 or int(pr.max()) >= grid.C):
+        raise ValueError(f"{fn}: a pair names a cloud outside [0, {grid.C})")
+    if not float(radius) > 0.0 or float(radius) >= 1e150:
+        raise ValueError(f"{fn}: radius must be positive and finite")
+    return grid, pr.tolist()
+
+
+def nn_radius(points: torch.Tensor, offsets, pairs, T: torch.Tensor, radius: float, grid: Optional[NNGrid] = None):
+    """One correspondence pass of the ICP on a ragged batch: points [total,3] float64, offsets [C+1], pairs [P,2] (source
+    cloud, target cloud), T [P,4,4] float64 -> (idx int32 [P,Nmax], d2 float64 [P,Nmax]), Nmax the largest source cloud:
+    for source point i of pair p the nearest target point to T[p] applied to it with d2 <= radius^2 (the smallest index
+    among equally near ones; -1 and +inf when there is none, and past the pair's source size)."""
+    _req_f64(points, "points"), _req_f64(T, "T")
+    grid, pr = _nn_operands("nn_radius", points, offsets, pairs, radius, grid)
+    P = len(pr)
+    if T.dim() != 3 or tuple(T.shape) != (P, 4, 4):
+        raise ValueError("nn_radius: T must be [P,4,4]")
+    dev = points.device
+    nmax = max([grid.sizes[s] for s, _ in pr], default=0)
+    idx = torch.full((P, nmax), -1, device=dev, dtype=torch.int32)
+    d2 = torch.full((P, nmax), float("inf"), device=dev, dtype=torch.float64)
+    live = [k for k, (s, t) in enumerate(pr) if grid.sizes[s] > 0 and grid.sizes[t] > 0]
+    if not live:
+        return idx, d2
+    pd = torch.tensor(pr, dtype=torch.int32).to(dev)
+    check(lib().lc_nn_radius(grid.points.data_ptr(), grid.offsets.data_ptr(), grid.C, grid.total, grid.buf.data_ptr(),
+                             pd.data_ptr(), T.contiguous().data_ptr(), P, nmax, float(radius), idx.data_ptr(),
+                             d2.data_ptr(), _stream()), "lc_nn_radius")
+    return idx, d2
+
+
+def icp_point_to_point(points: torch.Tensor, offsets, pairs, radius: float, init: Optional[torch.Tensor] = None,
+                       max_iteration: int = 30, relative_fitness: float = 1e-6, relative_rmse: float = 1e-6,
+                       grid: Optional[NNGrid] = None):
+    """Point-to-point ICP of every (source, target) pair of a ragged batch, the whole loop enqueued at once (Open3D
+    registration_icp with TransformationEstimationPointToPoint, restated: DESIGN.md section 5p) ->
+    (T [P,4,4] float64, fitness [P] float64, inlier_rmse [P] float64, iterations [P] int32).  init: [P,4,4] or None
+    (identity).  A pair with an empty cloud keeps its initial transform with fitness 0 and launches nothing."""
+    _req_f64(points, "points")
+    grid, pr = _nn_operands("icp_point_to_point", points, offsets, pairs, radius, grid)
+    P = len(pr)
+    dev = points.device
+    if int(max_iteration) < 0:
+        raise ValueError("icp_point_to_point: max_iteration >= 0")
+    if init is None:
+        T = torch.eye(4, device=dev, dtype=torch.float64).repeat(P, 1, 1)
+    else:
+        _req_f64(init, "init")
+        if tuple(init.shape) != (P, 4, 4):
+            raise ValueError("icp_point_to_point: init must be [P,4,4]")
+        T = init.contiguous().clone()
+    fitness = torch.zeros(P, device=dev, dtype=torch.float64)
+    rmse = torch.zeros(P, device=dev, dtype=torch.float64)
+    iters = torch.zeros(P, device=dev, dtype=torch.int32)
+    nmax = max([grid.sizes[s] for s, t in pr if grid.sizes[t] > 0], default=0)
+    if nmax == 0:
+        return T, fitness, rmse, iters
+    pd = torch.tensor(pr, dtype=torch.int32).to(dev)
+    nbytes = int(lib().lc_icp_scratch_bytes(P, nmax))
+    if nbytes <= 0:
+        raise ValueError("icp_point_to_point: more pairs than lc_icp_run takes")
+    scratch = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+    check(lib().lc_icp_run(grid.points.data_ptr(), grid.offsets.data_ptr(), grid.C, grid.total, grid.buf.data_ptr(),
+                           pd.data_ptr(), P, nmax, float(radius), int(max_iteration), float(relative_fitness),
+                           float(relative_rmse), T.data_ptr(), fitness.data_ptr(), rmse.data_ptr(), iters.data_ptr(),
+                           scratch.data_ptr(), _stream()), "lc_icp_run")
+    return T, fitness, rmse, iters
+
+
 def roiaware_pool3d_forward(rois, pts, pts_feature, out_size, max_pts_each_voxel: int, method: int):
     """-> (pooled [N,X,Y,Z,C], pts_idx_of_voxels int32 [N,X,Y,Z,max_pts], argmax int32 [N,X,Y,Z,C])."""
     for n_, t_ in (("rois", rois), ("pts", pts), ("pts_feature", pts_feature)):

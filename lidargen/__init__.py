@@ -15,11 +15,12 @@ class _AliasFinder(importlib.abc.MetaPathFinder, importlib.abc.Loader):
         if name == "lidargen" or name.startswith("lidargen."):
             real = _REAL + name[len("lidargen"):]
             try:
-                if importlib.util.find_spec(real) is None:
+                found = importlib.util.find_spec(real)
+                if found is None:
                     return None
             except ModuleNotFoundError:
                 return None
-            return importlib.util.spec_from_loader(name, self)
+            return importlib.util.spec_from_loader(name, self, origin=found.origin)   # (runpy: sys.argv[0])
         return None
 
     def create_module(self, spec):
@@ -27,6 +28,11 @@ class _AliasFinder(importlib.abc.MetaPathFinder, importlib.abc.Loader):
 
     def exec_module(self, module):
         pass
+
+    def get_code(self, name):
+        # `python -m lidargen.x.y` (runpy) asks the loader for the module's code: the real module's
+        real = _REAL + name[len("lidargen"):]
+        return importlib.util.find_spec(real).loader.get_code(real)
 
 
 if not any(isinstance(f, _AliasFinder) for f in sys.meta_path):
