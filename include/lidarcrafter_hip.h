@@ -1174,6 +1174,48 @@ int lc_icp_run(const double* points, const int32_t* offsets, int C, int64_t tota
                int P, int max_src, double radius, int max_iteration, double relative_fitness, double relative_rmse, double* T,
                double* fitness, double* inlier_rmse, int32_t* iterations, void* scratch, lc_stream_t s);
 
+/* ---------------------------------------------------------------------------------------------
+ * GLENet box sampler and rotated IoU of the RGF object metric (csrc/glenet.hip): the reference's
+ * lidargen/metrics/models/glenet/{point_net,model,loss_utils}.py and eval_utils/eval_utils.py.  DEVICE memory, contiguous
+ * float32 / int32 (variance, mean_overlap: float64); no atomics, an object's / a row's / a pair's bits depend on its own
+ * operands only.  Null pointers and sizes < 1: LC_EINVAL before any launch.
+ * A ragged batch: points [total,3], offsets [B+1] int32, object b owns rows offsets[b] ... offsets[b+1]-1; offsets that do
+ * not describe rows of `points` make an empty object, never an access outside the operand.  total < 2^31 (LC_EUNSUP).
+ *   lc_segment_center_fwd: mean [B,3] = float32(sum in float64 / n) per object (per-thread strided partial sums, a fixed tree;
+ *     0 for an empty object); out[i] = float32((double)(p[i] - mean) / (sx, sy, sz)), the difference in float32.  Scales > 0.
+ *   lc_glenet_trunk_fwd: rows r < R, object b = r mod B (a [D,B] grid of draws and objects, R = D B).  Row r reads its K
+ *     points as norm[offsets[b] + choice[r K + j]] (an index is clamped into the object's range; an empty object reads
+ *     zeros).  featA [512,R] = max over the K points of w3 relu(w2 relu(w1 p + b1) + b2) + b3 (PointNetfeat's trunk, w1
+ *     [64,3], w2 [128,64], w3 [512,128] row-major, w2 / w3 16-byte aligned, BatchNorm folded by the caller, scale included);
+ *     featS [8,R] the same for SimPointNetfeat's 3 -> 8 -> 8 -> 8 (sw1 [8,3], sw2, sw3 [8,8]), every output an fma chain over
+ *     ascending input channel from the bias.  Both CHANNEL-MAJOR: the [1,C,R] operand of lc_pointmlp_conv_fwd.  Exact fp32
+ *     on the f32-input MFMA in the k order of lc_pointnet_trunk_fwd; tails past K masked with -inf.  Any K >= 1 (< 2^24),
+ *     any R < 2^31: the row is the block index.
+ *   lc_rbox_inter_fwd: corners_g, corners_q [N,8] (x0 y0 ... x3 y3) -> pts [N,16] (the vertices in the order compute_vertex
+ *     finds them: corners of g inside q -- with the extra test adad > 0 and abab > 0 --, corners of q inside g, edge i of g
+ *     against edge j of q row-major; a ninth vertex is skipped; zeros past cnt), cnt [N], area [N] (sort_vertex: descending
+ *     angle in [0, 2 * 3.1415926) about the float32 centroid, stable, unused slots as angle 0, the angle a float64 atan2
+ *     rounded to float32; area_polygon: a fan from the first sorted vertex, abs per triangle).  One thread per pair, every
+ *     float32 operation rounded on its own (no contraction).  The reference's quirks are kept: two identical boxes give 0.
+ *   lc_riou3d_paired_fwd: boxes (x, y, z, dx, dy, dz, ry) in the first 7 of ldg / ldq (>= 7) columns: clamp to +-200,
+ *     rbbox_to_corners, the intersection above, the height overlap, inter / (vol_g + vol_q - inter) -> iou [N].
+ *   lc_glenet_score_fwd: box [D,B,9] (the sampler's output), gt [B,7], both normalised.  Decode: centres times (diag, diag,
+ *     dza) -- diag a float64 factor, the product rounded once --, sizes exp(.) times (dxa, dya, dza); pred [D,B,9] the decoded
+ *     box (columns 7, 8 copied), overlap [D,B] = the paired IoU of the decoded gt and draw.  Then in draw order and float64:
+ *     variance [B,7] the population variance over the draws of columns 0..5 and of sin(w - floor(w / 2 pi) 2 pi), w = ry -
+ *     gt ry; mean_overlap [B].  One wave per object, lane = draw (any D). */
+int lc_segment_center_fwd(const float* points, const int32_t* offsets, int B, int64_t total, double sx, double sy, double sz,
+                          float* out, float* mean, lc_stream_t s);
+int lc_glenet_trunk_fwd(const float* norm, int64_t total, const int32_t* offsets, const int32_t* choice, int B, int K,
+                        int64_t R, const float* w1, const float* b1, const float* w2, const float* b2, const float* w3,
+                        const float* b3, const float* sw1, const float* sb1, const float* sw2, const float* sb2,
+                        const float* sw3, const float* sb3, float* featA, float* featS, lc_stream_t s);
+int lc_rbox_inter_fwd(const float* corners_g, const float* corners_q, int N, float* pts, int32_t* cnt, float* area,
+                      lc_stream_t s);
+int lc_riou3d_paired_fwd(const float* g, int ldg, const float* q, int ldq, int N, float* iou, lc_stream_t s);
+int lc_glenet_score_fwd(const float* box, const float* gt, int D, int B, double diag, float dxa, float dya, float dza,
+                        float* pred, float* overlap, double* variance, double* mean_overlap, lc_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

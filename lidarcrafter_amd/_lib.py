@@ -229,6 +229,11 @@ SIGNATURES = {
     "lc_nn_radius": (i32, [vp, vp, i32, i64, vp, vp, vp, i32, i32, f64, vp, vp, vp]),
     "lc_icp_scratch_bytes": (i64, [i32, i32]),
     "lc_icp_run": (i32, [vp, vp, i32, i64, vp, vp, i32, i32, f64, i32, f64, f64, vp, vp, vp, vp, vp, vp]),
+    "lc_segment_center_fwd": (i32, [vp, vp, i32, i64, f64, f64, f64, vp, vp, vp]),
+    "lc_glenet_trunk_fwd": (i32, [vp, i64, vp, vp, i32, i32, i64] + [vp] * 12 + [vp, vp, vp]),
+    "lc_rbox_inter_fwd": (i32, [vp, vp, i32, vp, vp, vp, vp]),
+    "lc_riou3d_paired_fwd": (i32, [vp, i32, vp, i32, i32, vp, vp]),
+    "lc_glenet_score_fwd": (i32, [vp, vp, i32, i32, f64, f32, f32, f32, vp, vp, vp, vp, vp]),
 }
 
 _lib = None

@@ -2,7 +2,7 @@
 // PointNetfeat (lidargen/metrics/extractor/pointnet.py) followed by the max over the points, BatchNorm folded into the
 // weights by the caller.  Nothing wider than the 3 input channels is read from memory and only per-tile channel maxima
 // are written.
-//   pn_trunk_kernel   one block = PN_T points of one cloud, 4 waves, 64 KiB of LDS: two blocks per CU, so one block's
+//   pn_trunk_kernel   (its three stages are in csrc/pointnet_trunk.h)  one block = PN_T points of one cloud, 4 waves, 64 KiB of LDS: two blocks per CU, so one block's
 //                     layer 1, weight loads and reductions run under the other block's MFMAs.
 //       layer 1 (K = 3, the optional 3x3 transform in front of it) on the vector ALUs -> h1 [64][PN_T] in LDS
 //       layer 2 on v_mfma_f32_32x32x2_f32: wave w owns output channels 32 w .. 32 w + 31, its 32 x 64 slice of W2 sits
@@ -19,12 +19,12 @@
 // blocks depend on nothing but the cloud, and the maxima are merged in a fixed order without atomics: the same bits for
 // a cloud in every batch and every run.  A point (0,0,0) is a point like any other.
 #include "common.h"
-#include "f16x2.h"      // mfma_row
+#include "pointnet_trunk.h"   // the three stages of a tile: one definition shared with csrc/glenet.hip
 
 namespace {
 
-constexpr int PN_T = 128;                     // points per block
-constexpr int PN_C1 = 64, PN_C2 = 128, PN_C3 = 1024;
+constexpr int PN_T = PNT_T;                   // points per block
+constexpr int PN_C1 = PNT_C1, PN_C2 = PNT_C2, PN_C3 = 1024;
 
 __global__ __launch_bounds__(256, 2) void pn_trunk_kernel(const float* __restrict__ x, long long x_bs,
                                                       const float* __restrict__ trans, const float* __restrict__ w1,
@@ -57,86 +57,19 @@ __global__ __launch_bounds__(256, 2) void pn_trunk_kernel(const float* __restric
             const float r2 = fmaf(q2, t[8], fmaf(q1, t[5], q0 * t[2]));
             q0 = r0, q1 = r1, q2 = r2;
         }
-#pragma unroll 8
-        for (int c = c0; c < c0 + 32; ++c) {
-            const float v = fmaf(w1[c * 3 + 2], q2, fmaf(w1[c * 3 + 1], q1, fmaf(w1[c * 3], q0, b1[c])));
-            h1[c * PN_T + p] = fmaxf(v, 0.f);
-        }
+        pnt_layer1(h1, p, c0, q0, q1, q2, w1, b1);
     }
     __syncthreads();
-
-    {   // layer 2: lane (j, h) holds W2[32 wave + j][32 h .. 32 h + 31]; column j of accumulator s is point 4 j + s
-        const f32x4* wp = reinterpret_cast<const f32x4*>(w2 + (size_t)(wave * 32 + j) * PN_C1 + h * 32);
-        f32x4 a[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) a[i] = wp[i];
-        f32x16 acc[4];
-#pragma unroll
-        for (int s = 0; s < 4; ++s)
-#pragma unroll
-            for (int v = 0; v < 16; ++v) acc[s][v] = 0.f;
-#pragma unroll
-        for (int kk = 0; kk < 32; ++kk) {
-            if ((kk & 7) == 0) __builtin_amdgcn_sched_barrier(0);   // LDS reads run at most 8 steps ahead
-            const f32x4 bv = *reinterpret_cast<const f32x4*>(&h1[(h * 32 + kk) * PN_T + 4 * j]);
-#pragma unroll
-            for (int s = 0; s < 4; ++s)
-                acc[s] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[kk >> 2][kk & 3], bv[s], acc[s], 0, 0, 0);
-        }
-        __syncthreads();                      // every wave has read h1
-#pragma unroll
-        for (int v = 0; v < 16; ++v) {
-            const int c = wave * 32 + mfma_row(v, h);
-            const float bias = b2[c];
-            f32x4 o;
-#pragma unroll
-            for (int s = 0; s < 4; ++s) o[s] = fmaxf(acc[s][v] + bias, 0.f);
-            *reinterpret_cast<f32x4*>(&h2[c * PN_T + 4 * j]) = o;
-        }
-    }
+    pnt_layer2(h2, w2, b2, wave, j, h);
     __syncthreads();
 
-    // layer 3: chunk = 32 output channels; lane (j, h) holds W3[32 chunk + j][64 h .. 64 h + 63]
+    // layer 3 in 32 chunks of 32 output channels, 8 per wave
     float* out = part + ((size_t)b * tiles + tile) * PN_C3;
     const int nvalid = N - t0;                // >= 1; < PN_T only in the cloud's last tile
-    const float ninf = -__builtin_huge_valf();
     for (int it = 0; it < PN_C3 / 32 / 4; ++it) {
         const int chunk = wave + 4 * it;
-        f32x4 a[16];
-        {
-            const f32x4* wp = reinterpret_cast<const f32x4*>(w3 + (size_t)(chunk * 32 + j) * PN_C2 + h * 64);
-#pragma unroll
-            for (int i = 0; i < 16; ++i) a[i] = wp[i];
-        }
-        f32x16 acc[4];
-#pragma unroll
-        for (int s = 0; s < 4; ++s)
-#pragma unroll
-            for (int v = 0; v < 16; ++v) acc[s][v] = 0.f;
-#pragma unroll
-        for (int kk = 0; kk < 64; ++kk) {
-            if ((kk & 7) == 0) __builtin_amdgcn_sched_barrier(0);   // LDS reads run at most 8 steps ahead
-            const f32x4 bv = *reinterpret_cast<const f32x4*>(&h2[(h * 64 + kk) * PN_T + 4 * j]);
-#pragma unroll
-            for (int s = 0; s < 4; ++s)
-                acc[s] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[kk >> 2][kk & 3], bv[s], acc[s], 0, 0, 0);
-        }
-        if (nvalid < PN_T) {
-#pragma unroll
-            for (int s = 0; s < 4; ++s)
-                if (4 * j + s >= nvalid) {
-#pragma unroll
-                    for (int v = 0; v < 16; ++v) acc[s][v] = ninf;
-                }
-        }
         float m[16];
-#pragma unroll
-        for (int v = 0; v < 16; ++v) {
-            float t = fmaxf(fmaxf(acc[0][v], acc[1][v]), fmaxf(acc[2][v], acc[3][v]));
-#pragma unroll
-            for (int o = 16; o > 0; o >>= 1) t = fmaxf(t, __shfl_xor(t, o, 64));   // stays inside the half wave
-            m[v] = t;
-        }
+        pnt_layer3_chunk(h2, w3, chunk, j, h, nvalid, m);
         if (j == 0) {
 #pragma unroll
             for (int v = 0; v < 16; ++v) out[chunk * 32 + mfma_row(v, h)] = m[v];

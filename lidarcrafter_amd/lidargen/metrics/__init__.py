@@ -7,7 +7,9 @@ csrc/spconv.hip) and the Frechet Point-Voxel Distance (`models.spvcnn`, `metric_
 csrc/rangenet.hip), with its sibling FRD of the reference's own evaluator (`extractor.rangenet`, `eval_utils.compute_frd`),
 and the object half: the PointMLP extractor (`extractor.pointmlp`; farthest point sampling, k nearest neighbours and grouped
 dense layers in csrc/pointmlp.hip), `datasets.nuscenes_object_dataset.NuscObject`, `fg_object` and
-`eval_utils.compute_obj_scores`; the sequence metrics TTCE and TCD (`temporal`; point-to-point ICP in csrc/icp.hip)."""
+`eval_utils.compute_obj_scores`, and RGF on the GLENet box sampler (`models.glenet`, `datasets.object_uncertainty_dataset`,
+`fg_object.compute_rgf`; gathered trunk, rotated IoU and the score reduction in csrc/glenet.hip); the sequence metrics TTCE and
+TCD (`temporal`; point-to-point ICP in csrc/icp.hip)."""
 import os
 
 # a score line as the reference prints it: a 50-column rule above and below `|<16 blanks>NAME:1.2345E+00<17 blanks>|`

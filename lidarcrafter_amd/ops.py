@@ -3002,3 +3002,15 @@ def _wrap_public_ops():
 
 
 _wrap_public_ops()
+
+
+# the GLENet / rotated-IoU ops of csrc/glenet.hip live in ops_glenet (which imports this module): resolved on first use
+_GLENET_OPS = ("segment_center", "glenet_trunk", "rbox_intersection", "riou3d_paired", "glenet_score")
+
+
+def __getattr__(name):
+    if name in _GLENET_OPS:
+        from . import ops_glenet
+
+        return getattr(ops_glenet, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -443,3 +443,11 @@ def seeded_fill_pointmlp(module: torch.nn.Module, salt: int = 0) -> torch.nn.Mod
             v = 0.1 * torch.randn(p.shape, generator=g)
         p.copy_(v.to(device=p.device, dtype=p.dtype))
     return module
+
+
+@torch.no_grad()
+def seeded_fill_glenet(module: torch.nn.Module, salt: int = 0) -> torch.nn.Module:
+    """Seeded weights for a GLENet `Generator` of either module tree: `seeded_fill_pointnet`, whose key suffixes
+    (`running_mean`, `running_var`, `bn3.weight` -- here the BatchNorm in front of the max over an object's points) are
+    GLENet's too.  `global_step` is left alone."""
+    return seeded_fill_pointnet(module, salt)
