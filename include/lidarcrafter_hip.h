@@ -527,6 +527,30 @@ int lc_qk_norm_cm_bwd(const float* x, int64_t x_bs, int64_t x_cs, const float* g
 int lc_attention_jvp_fwd(const float* q, const float* k, const float* v, const float* dq, const float* dk,
                          const float* dv, float* o, float* lse, float* dout, int BH, int Lq, int Lk, int dqk, int dv_ch,
                          float scale, lc_stream_t s);
+/* Which way a call of the tangent kernels runs (pure host code, no GPU needed; the launchers and kernels switch on the
+ * same functions, csrc/flow_jvp_route.h and csrc/gn_apply_route.h).  Addresses are passed modulo 16.  Each returns LC_OK,
+ * or the code of its entry where that refuses a size (LC_EINVAL not positive or C % G, LC_EUNSUP beyond a limit).
+ * lc_groupnorm_jvp_route: lc_groupnorm_jvp_stats / lc_groupnorm_jvp_apply_train.  Fills
+ *   out[0] chunk          elements per statistics block (4096 or 16384)
+ *   out[1] chunks         statistics blocks per (sample, group): lc_groupnorm_jvp_partials_elems = 4 B G out[1]
+ *   out[2] stats branch   1 every (sample, group) is read as float4, 0 none is, 2 it differs by sample
+ *   out[3] causes         seen on any (sample, group): bit 0 n % 4 (n = C / G H W), bit 1 a group of x off 16 bytes (either
+ *                         sends the group to the scalar loop), bit 2 a group of dx off 16 bytes where x is not (the float4
+ *                         loop with scalar loads of dx)
+ *   out[4] dx loads       of the groups in the float4 loop: 1 all load dx as float4, 0 none does, 2 it differs by sample
+ *   out[5] slabs          blocks per plane of the apply pass (ceil(H W / 4096))
+ *   out[6] cpb            channels per apply block (1, 2, 4, ...: lc_groupnorm_apply_train's rule)
+ *   out[7] amax slots     blocks of the apply pass = lc_groupnorm_amax_partials(B, C, H, W, G, 0)
+ * lc_qk_norm_cm_route: lc_qk_norm_cm_jvp / lc_qk_norm_cm_bwd.  Fills out[0] channels held per token (16, 32 or 64),
+ *   out[1] 256-token blocks per (sample, head), out[2] fp64 partials of dg (= lc_qk_norm_cm_bwd_partials), out[3] trips of
+ *   the reduce's 256-lane loop over them.
+ * lc_attention_jvp_route: lc_attention_jvp_fwd.  Fills out[0] padded head width (32 or 64), out[1] query rows per block
+ *   (64 or 32), out[2] query blocks, out[3] 16-key tiles, out[4] keys in the last tile, out[5] query rows in the last
+ *   block, out[6] / out[7] padded channels inside the last lane that holds a channel of q, k / of v (8 channels per lane). */
+int lc_groupnorm_jvp_route(int B, int C, int H, int W, int G, int64_t x_bs, int64_t dx_bs, int x_addr_mod16,
+                           int dx_addr_mod16, int32_t* out /* [8] */);
+int lc_qk_norm_cm_route(int B, int heads, int d, int L, int32_t* out /* [4] */);
+int lc_attention_jvp_route(int BH, int Lq, int Lk, int dqk, int dv_ch, int32_t* out /* [8] */);
 /* Keys and values in UNIT FORM (round 6; csrc/attention_units.hip): the fp16 hi / lo split of lc_attention_f16x2_fwd
  * made once per step (or once per condition, for the step-invariant positional channels and the layout keys of
  * ObjectAwareCrossAttention, layout_unet_v1.py:431-476) instead of once per query block inside the attention kernel.

@@ -145,6 +145,9 @@ SIGNATURES = {
     "lc_qk_norm_cm_bwd_partials": (i64, [i32, i32, i32]),
     "lc_qk_norm_cm_bwd": (i32, [vp, i64, i64, vp, i64, i64, vp, vp, i64, i64, vp, vp, i32, i32, i32, i32, vp]),
     "lc_attention_jvp_fwd": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, vp]),
+    "lc_groupnorm_jvp_route": (i32, [i32, i32, i32, i32, i32, i64, i64, i32, i32, vp]),
+    "lc_qk_norm_cm_route": (i32, [i32, i32, i32, i32, vp]),
+    "lc_attention_jvp_route": (i32, [i32, i32, i32, i32, i32, vp]),
     "lc_attention_train_fwd": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, i32, vp, vp]),
     "lc_attention_bwd": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, vp]),
     "lc_attention_bwd_f16x2": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, vp, vp]),

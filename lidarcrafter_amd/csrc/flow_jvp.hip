@@ -19,20 +19,14 @@
 //    Exact fp32 on the vector ALUs (fma): 8 channels per lane, the lanes of a query row adjacent (4 for heads of <= 32
 //    channels, 8 for <= 64), 256 lanes per block, 16-key tiles of k, dk, v, dv in LDS.
 #include "common.h"
+#include "flow_jvp_route.h"
 
 namespace {
 
 // ---- GroupNorm ----------------------------------------------------------------------------------------------------------
 // (the chunking of the statistics partials: gn_chunk_elems / gn_chunks of common.h, shared with norm.hip)
-// launch shape of norm.hip's apply pass (gn_apply_grid): the partial maxima of |y| come out in the same count and order
-inline void gnj_apply_grid(int B, int C, int G, long long HW, int* slabs, int* cpb) {
-    int sl = (int)((HW + 4095) / 4096);
-    if (sl < 1) sl = 1;
-    int c = 1;
-    const int cpg = C / G;
-    while (c * 2 <= cpg && cpg % (c * 2) == 0 && HW * c * 2 <= 4096 && (long long)B * (C / (c * 2)) * sl >= 512) c *= 2;
-    *slabs = sl; *cpb = c;
-}
+// (the launch shape of the apply pass: lc_gn_apply_grid of gn_apply_route.h, norm.hip's, so the partial maxima of |y| come
+//  out in the same count and order; the branches below: flow_jvp_route.h, which lc_groupnorm_jvp_route reports)
 
 __global__ __launch_bounds__(256) void gn_jvp_stats_kernel(const float* __restrict__ x, long long x_bs,
                                                           const float* __restrict__ dx, long long dx_bs,
@@ -47,8 +41,8 @@ __global__ __launch_bounds__(256) void gn_jvp_stats_kernel(const float* __restri
     const long long hi = (lo + chunk_elems < n) ? lo + chunk_elems : n;
     const float piv = p[0];
     float s = 0.f, q = 0.f, sd = 0.f, sxd = 0.f;
-    if ((n & 3) == 0 && ((reinterpret_cast<uintptr_t>(p) & 15) == 0)) {
-        const bool dvec = (reinterpret_cast<uintptr_t>(dp) & 15) == 0;
+    if (lc_gnj_scalar_causes(n, (int)(reinterpret_cast<uintptr_t>(p) & 15)) == 0) {
+        const bool dvec = lc_gnj_dvec((int)(reinterpret_cast<uintptr_t>(dp) & 15));
         for (long long i = lo + threadIdx.x * 4; i < hi; i += 1024) {
             f32x4 v = *reinterpret_cast<const f32x4*>(p + i);
             f32x4 d;
@@ -161,7 +155,7 @@ struct QkArgs {
 
 template <int DMAX, bool BWD>
 __global__ __launch_bounds__(256) void qk_norm_jvp_kernel(QkArgs a) {
-    const int t = blockIdx.x * 256 + threadIdx.x;
+    const int t = blockIdx.x * LC_QKJ_TOKENS + threadIdx.x;
     const int bh = blockIdx.y;
     const int b = bh / a.heads, h = bh - b * a.heads;
     double gpart = 0.0;
@@ -226,7 +220,7 @@ __global__ __launch_bounds__(256) void qk_norm_dg_reduce_kernel(const double* __
 }
 
 // ---- attention ----------------------------------------------------------------------------------------------------------
-constexpr int JK = 16;      // keys per LDS tile
+constexpr int JK = LC_ATTNJ_JK;      // keys per LDS tile
 
 struct AttnJvpArgs {
     const float *q, *k, *v, *dq, *dk, *dv;
@@ -238,7 +232,7 @@ struct AttnJvpArgs {
 // D = padded head width (32 or 64) of q / k and v alike; lane j of a query row's LPQ lanes owns channels 8j .. 8j + 7
 template <int D>
 __global__ __launch_bounds__(256) void attn_jvp_kernel(AttnJvpArgs a) {
-    constexpr int PC = 8, LPQ = D / PC, QB = 256 / LPQ;
+    constexpr int PC = LC_ATTNJ_PC, LPQ = D / PC, QB = lc_attnj_rows(D);
     __shared__ float ks[D][JK + 1], dks[D][JK + 1], vs[D][JK + 1], dvs[D][JK + 1];
     const int bh = blockIdx.y;
     const int lj = threadIdx.x & (LPQ - 1);
@@ -272,8 +266,13 @@ __global__ __launch_bounds__(256) void attn_jvp_kernel(AttnJvpArgs a) {
             dvs[c][s] = cv ? a.dv[vb + (long long)c * a.Lk + key] : 0.0f;
         }
         __syncthreads();
-        const int nk = a.Lk - k0 < JK ? a.Lk - k0 : JK;
-        float s2[JK], ds[JK];
+        const int nk = lc_attnj_tile_keys(a.Lk, k0);
+        // qk[s]: the unscaled q . k.  The exponent of p is formed below as fma(qk, qscale, -m): one rounding of the
+        // DIFFERENCE.  Rounding qk * qscale first costs half an ulp of the score itself, 2^-16 at a common offset of 500 --
+        // a relative error of 1e-5 in p that differs from key to key (tests/test_flow_jvp_edges.py, the offset500 rows).
+        // The running maximum is still the rounded product: its rounding is common to every key of the row and cancels
+        // in O / l; lse = m + log2(l) gains what l carries of it.
+        float qk[JK], ds[JK];
         float mt = m;
 #pragma unroll
         for (int s = 0; s < JK; ++s) {
@@ -290,9 +289,9 @@ __global__ __launch_bounds__(256) void attn_jvp_kernel(AttnJvpArgs a) {
                 sp += __shfl_xor(sp, o, 64);
                 dp += __shfl_xor(dp, o, 64);
             }
-            s2[s] = s < nk ? sp * a.qscale : -INFINITY;
+            qk[s] = sp;
             ds[s] = dp * a.scale;
-            mt = fmaxf(mt, s2[s]);
+            mt = fmaxf(mt, s < nk ? sp * a.qscale : -INFINITY);
         }
         const float alpha = exp2f(m - mt);               // 0 on the first tile (m = -inf, mt finite)
         m = mt;
@@ -302,7 +301,7 @@ __global__ __launch_bounds__(256) void attn_jvp_kernel(AttnJvpArgs a) {
         for (int i = 0; i < PC; ++i) { O[i] *= alpha; T[i] *= alpha; }
 #pragma unroll
         for (int s = 0; s < JK; ++s) {
-            const float p = exp2f(s2[s] - m);            // 0 for keys past Lk
+            const float p = s < nk ? exp2f(fmaf(qk[s], a.qscale, -m)) : 0.0f;      // 0 for keys past Lk
             l += p;
             mu = fmaf(p, ds[s], mu);
             const float pds = p * ds[s];
@@ -362,7 +361,7 @@ extern "C" int lc_groupnorm_jvp_apply_train(const float* x, int64_t x_bs, const 
     const long long HW = (long long)H * W;
     const int nch = gn_chunks(B, G, (long long)(C / G) * HW);
     int slabs, cpb;
-    gnj_apply_grid(B, C, G, HW, &slabs, &cpb);
+    lc_gn_apply_grid(B, C, G, HW, &slabs, &cpb);
     hipLaunchKernelGGL(gn_jvp_apply_kernel, dim3(slabs, C / cpb, B), dim3(256), 0, lc_s(s), x, (long long)x_bs, dx,
                        (long long)dx_bs, partials, gamma, beta, scale, shift, dscale, dshift, (long long)ss_bs, y,
                        (long long)y_bs, dy, (long long)dy_bs, C, G, HW, nch, eps, act_silu, cpb, mean_rstd_out, amax_out,
@@ -371,15 +370,17 @@ extern "C" int lc_groupnorm_jvp_apply_train(const float* x, int64_t x_bs, const 
 }
 
 static int qk_norm_launch(const QkArgs& a, int B, bool bwd, lc_stream_t s) {
-    const dim3 grid((a.L + 255) / 256, B * a.heads);
+    const dim3 grid(lc_qkj_blocks(a.L), B * a.heads);
 #define LC_QKJ(DM)                                                                                       \
     do {                                                                                                 \
         if (bwd) hipLaunchKernelGGL((qk_norm_jvp_kernel<DM, true>), grid, dim3(256), 0, lc_s(s), a);    \
         else hipLaunchKernelGGL((qk_norm_jvp_kernel<DM, false>), grid, dim3(256), 0, lc_s(s), a);       \
     } while (0)
-    if (a.d <= 16) LC_QKJ(16);
-    else if (a.d <= 32) LC_QKJ(32);
-    else LC_QKJ(64);
+    switch (lc_qkj_dmax(a.d)) {
+        case 16: LC_QKJ(16); break;
+        case 32: LC_QKJ(32); break;
+        default: LC_QKJ(64); break;
+    }
 #undef LC_QKJ
     return lc_launch_status();
 }
@@ -398,7 +399,7 @@ extern "C" int lc_qk_norm_cm_jvp(const float* x, int64_t x_bs, int64_t x_cs, con
 
 extern "C" int64_t lc_qk_norm_cm_bwd_partials(int B, int heads, int L) {
     if (B <= 0 || heads <= 0 || L <= 0) return 0;
-    return (int64_t)((L + 255) / 256) * B * heads;
+    return (int64_t)lc_qkj_partials(B, heads, L);
 }
 
 extern "C" int lc_qk_norm_cm_bwd(const float* x, int64_t x_bs, int64_t x_cs, const float* gy, int64_t gy_bs,
@@ -425,9 +426,24 @@ extern "C" int lc_attention_jvp_fwd(const float* q, const float* k, const float*
         return LC_EINVAL;
     if (dqk > 64 || dv_ch > 64 || BH > 65535) return LC_EUNSUP;
     AttnJvpArgs a{q, k, v, dq, dk, dv, o, lse, dout, Lq, Lk, dqk, dv_ch, scale, scale * 1.4426950408889634f};
-    if (dqk <= 32 && dv_ch <= 32)
-        hipLaunchKernelGGL(attn_jvp_kernel<32>, dim3((Lq + 63) / 64, BH), dim3(256), 0, lc_s(s), a);
+    if (lc_attnj_width(dqk, dv_ch) == 32)
+        hipLaunchKernelGGL(attn_jvp_kernel<32>, dim3(lc_attnj_qblocks(Lq, 32), BH), dim3(256), 0, lc_s(s), a);
     else
-        hipLaunchKernelGGL(attn_jvp_kernel<64>, dim3((Lq + 31) / 32, BH), dim3(256), 0, lc_s(s), a);
+        hipLaunchKernelGGL(attn_jvp_kernel<64>, dim3(lc_attnj_qblocks(Lq, 64), BH), dim3(256), 0, lc_s(s), a);
     return lc_launch_status();
+}
+
+// ---- which way a call runs (pure host code: flow_jvp_route.h) ------------------------------------------------------------
+extern "C" int lc_groupnorm_jvp_route(int B, int C, int H, int W, int G, int64_t x_bs, int64_t dx_bs, int x_addr_mod16,
+                                      int dx_addr_mod16, int32_t* out) {
+    if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || G <= 0 || C % G) return LC_EINVAL;
+    const long long n = (long long)(C / G) * H * W;
+    return lc_gnj_route(B, C, H, W, G, x_bs, dx_bs, x_addr_mod16, dx_addr_mod16, gn_chunk_elems(B, G, n), gn_chunks(B, G, n),
+                        out);
+}
+
+extern "C" int lc_qk_norm_cm_route(int B, int heads, int d, int L, int32_t* out) { return lc_qkj_route(B, heads, d, L, out); }
+
+extern "C" int lc_attention_jvp_route(int BH, int Lq, int Lk, int dqk, int dv_ch, int32_t* out) {
+    return lc_attnj_route(BH, Lq, Lk, dqk, dv_ch, out);
 }

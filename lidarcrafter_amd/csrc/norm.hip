@@ -5,6 +5,7 @@
 // apply reads once and writes once.  A group is a contiguous span of (C/G)*H*W floats in NCHW.
 #include "common.h"
 #include "f16x2.h"
+#include "gn_apply_route.h"
 #include "gn_bwd_route.h"
 #include "stats_entry.h"
 
@@ -532,28 +533,13 @@ extern "C" int lc_groupnorm_stats(const float* x, int64_t x_bs, double* partials
     return lc_launch_status();
 }
 
-namespace {
-// launch shape of gn_apply_kernel: slabs of >= 4096 elements; small planes: several channels of a group per block, so the
-// per-block fold of the partials (fp64 divide + sqrt) is paid once per >= 4096 elements while >= 512 blocks remain
-inline void gn_apply_grid(int B, int C, int G, long long HW, int* slabs, int* cpb) {
-    int sl = (int)((HW + 4095) / 4096);
-    if (sl < 1) sl = 1;
-    int c = 1;
-    const int cpg = C / G;
-    while (c * 2 <= cpg && cpg % (c * 2) == 0 && HW * c * 2 <= 4096 && (long long)B * (C / (c * 2)) * sl >= 512) c *= 2;
-    *slabs = sl; *cpb = c;
-}
-}  // namespace
-
 // floats lc_groupnorm_apply_train (backward == 0) / lc_groupnorm_bwd_train (backward != 0) write through amax_out: one
 // partial maximum per block of their apply pass
 extern "C" int64_t lc_groupnorm_amax_partials(int B, int C, int H, int W, int G, int backward) {
     if (B <= 0 || C <= 0 || G <= 0 || C % G || H <= 0 || W <= 0) return 0;
     // backward: one per block of gn_bwd_apply_kernel, whose slab count is the launcher's (gn_bwd_route.h)
     if (backward) return (int64_t)lc_gn_bwd_slabs((long long)H * W) * C * B;
-    int slabs, cpb;
-    gn_apply_grid(B, C, G, (long long)H * W, &slabs, &cpb);
-    return (int64_t)slabs * (C / cpb) * B;
+    return (int64_t)lc_gn_apply_blocks(B, C, G, (long long)H * W);       // (gn_apply_route.h: gn_apply_kernel's grid)
 }
 
 extern "C" int lc_groupnorm_apply_train(const float* x, int64_t x_bs, const double* partials,
@@ -565,7 +551,7 @@ extern "C" int lc_groupnorm_apply_train(const float* x, int64_t x_bs, const doub
     const long long HW = (long long)H * W;
     const int nch = gn_chunks(B, G, (long long)(C / G) * HW);
     int slabs, cpb;
-    gn_apply_grid(B, C, G, HW, &slabs, &cpb);
+    lc_gn_apply_grid(B, C, G, HW, &slabs, &cpb);
     hipLaunchKernelGGL(gn_apply_kernel, dim3(slabs, C / cpb, B), dim3(256), 0, lc_s(s), x,
                        (long long)x_bs, partials, gamma, beta, scale, shift, (long long)ss_bs, y,
                        (long long)y_bs, C, G, HW, nch, eps, act_silu, cpb, mean_rstd_out, amax_out);

@@ -34,6 +34,16 @@ def test_library_exports_every_symbol():
     # statistics blocks: 64 KiB chunks, 16 KiB when that would leave fewer than 512 blocks
     assert handle.lc_groupnorm_partials_elems(32, 64, 32, 1024, 8) == 32 * 8 * 16 * 2
     assert handle.lc_groupnorm_partials_elems(2, 64, 32, 1024, 8) == 2 * 8 * 64 * 2
+    # the route queries of the tangent kernels (csrc/flow_jvp_route.h): the same chunks, the apply pass's slot count
+    import ctypes
+
+    out = (ctypes.c_int32 * 8)()
+    assert handle.lc_groupnorm_jvp_route(2, 64, 32, 1024, 8, 64 * 32 * 1024, 64 * 32 * 1024, 0, 0, out) == 0
+    assert list(out)[:3] == [4096, 64, 1] and out[7] == handle.lc_groupnorm_amax_partials(2, 64, 32, 1024, 8, 0)
+    assert handle.lc_groupnorm_jvp_partials_elems(2, 64, 32, 1024, 8) == 2 * 8 * out[1] * 4
+    assert handle.lc_qk_norm_cm_route(8, 8, 64, 512, out) == 0 and list(out)[:4] == [64, 2, 128, 1]
+    assert handle.lc_qk_norm_cm_bwd_partials(8, 8, 512) == 128
+    assert handle.lc_attention_jvp_route(64, 512, 512, 64, 64, out) == 0 and list(out)[:6] == [64, 32, 16, 32, 16, 32]
 
 
 def test_argument_checks_refuse_before_any_launch():
