@@ -1240,6 +1240,37 @@ int lc_riou3d_paired_fwd(const float* g, int ldg, const float* q, int ldq, int N
 int lc_glenet_score_fwd(const float* box, const float* gt, int D, int B, double diag, float dxa, float dya, float dza,
                         float* pred, float* overlap, double* variance, double* mean_overlap, lc_stream_t s);
 
+/* ---------------------------------------------------------------------------------------------
+ * Rotated BEV overlap / IoU, 3-D IoU and NMS of lidargen.ops.iou3d_nms (csrc/iou3d_nms.hip over the geometry of
+ * csrc/iou3d_box.h): the reference's lidargen/ops/iou3d_nms.  Boxes are contiguous float32 rows
+ * [x, y, z, dx, dy, dz, heading] in DEVICE memory (the two *_host entries: HOST memory, no GPU touched).  Every entry checks
+ * its arguments before any launch: null pointers and negative counts LC_EINVAL; a count of 0 returns LC_OK with nothing
+ * launched and nothing dereferenced beyond the null checks.  No contraction into fused multiply-adds anywhere; a pair's
+ * bits depend on its two rows only.  The geometry is not the GLENet metric's (lc_riou3d_paired_fwd): two identical boxes
+ * overlap in their whole area here.
+ *   mode: 0 the BEV overlap area, 1 the BEV IoU overlap / max(sa + sb - overlap, 1e-8), 2 the 3-D IoU: with
+ *     h = clamp(min(za + dza/2, zb + dzb/2) - max(za - dza/2, zb - dzb/2), min=0), o3 = overlap * h and v = dx * dy * dz
+ *     (left to right): o3 / clamp(va + vb - o3, min=1e-6), every operation rounded to float32 on its own.
+ *   lc_boxes_iou_pairwise_fwd: out [na, nb] row-major.  na * nb <= 2^38, mode in 0..2 (LC_EUNSUP otherwise).
+ *   lc_boxes_iou_aligned_fwd: out [n], row i of a with row i of b, mode 0 or 2 (LC_EUNSUP otherwise); the same kernel, so the
+ *     same bits as entry [i, i] of the pairwise form.
+ *   lc_nms_mask_fwd: mask [n, ceil(n / 64)] 64-bit words, bit c of word [r, w] set iff iou(r, 64 w + c) > thresh and
+ *     64 w + c > r; iou is the BEV IoU (normal == 0) or the IoU of the unrotated extents (normal != 0).  Only the words
+ *     with w >= r / 64 are written; the others are left as they were.  n <= LC_NMS_MAX_BOXES (LC_EUNSUP above: the mask
+ *     would pass 512 MiB).
+ *   lc_nms_select_fwd: the greedy walk over such a mask in index order -- box i is kept unless an earlier kept box has
+ *     its bit set -- on the device, reading only the words lc_nms_mask_fwd writes.  keep [n] receives the kept indices in
+ *     ascending order, *count their number (device memory both; entries of keep past *count are not written).
+ *   lc_boxes_iou_bev_host / lc_boxes_overlap_bev_host: the BEV IoU / the overlap area (and, where cnt is not null, the
+ *     number of polygon points found, [na, nb] int32) of every pair on the CPU, through the same header. */
+#define LC_NMS_MAX_BOXES 65536
+int lc_boxes_iou_pairwise_fwd(const float* boxes_a, int na, const float* boxes_b, int nb, int mode, float* out, lc_stream_t s);
+int lc_boxes_iou_aligned_fwd(const float* boxes_a, const float* boxes_b, int n, int mode, float* out, lc_stream_t s);
+int lc_nms_mask_fwd(const float* boxes, int n, float thresh, int normal, uint64_t* mask, lc_stream_t s);
+int lc_nms_select_fwd(const uint64_t* mask, int n, int64_t* keep, int32_t* count, lc_stream_t s);
+int lc_boxes_iou_bev_host(const float* boxes_a, int na, const float* boxes_b, int nb, float* out);
+int lc_boxes_overlap_bev_host(const float* boxes_a, int na, const float* boxes_b, int nb, float* out, int32_t* cnt);
+
 #ifdef __cplusplus
 }
 #endif

@@ -237,6 +237,12 @@ SIGNATURES = {
     "lc_rbox_inter_fwd": (i32, [vp, vp, i32, vp, vp, vp, vp]),
     "lc_riou3d_paired_fwd": (i32, [vp, i32, vp, i32, i32, vp, vp]),
     "lc_glenet_score_fwd": (i32, [vp, vp, i32, i32, f64, f32, f32, f32, vp, vp, vp, vp, vp]),
+    "lc_boxes_iou_pairwise_fwd": (i32, [vp, i32, vp, i32, i32, vp, vp]),
+    "lc_boxes_iou_aligned_fwd": (i32, [vp, vp, i32, i32, vp, vp]),
+    "lc_nms_mask_fwd": (i32, [vp, i32, f32, i32, vp, vp]),
+    "lc_nms_select_fwd": (i32, [vp, i32, vp, vp, vp]),
+    "lc_boxes_iou_bev_host": (i32, [vp, i32, vp, i32, vp]),
+    "lc_boxes_overlap_bev_host": (i32, [vp, i32, vp, i32, vp, vp]),
 }
 
 _lib = None

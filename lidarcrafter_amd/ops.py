@@ -3008,9 +3008,18 @@ _wrap_public_ops()
 _GLENET_OPS = ("segment_center", "glenet_trunk", "rbox_intersection", "riou3d_paired", "glenet_score")
 
 
+# likewise the rotated-box overlap / IoU / NMS ops of csrc/iou3d_nms.hip in ops_iou3d
+_IOU3D_OPS = ("boxes_overlap_bev", "boxes_iou_bev", "boxes_iou3d", "boxes_aligned_iou3d", "nms_mask", "nms_select", "nms",
+              "boxes_iou_bev_host")
+
+
 def __getattr__(name):
     if name in _GLENET_OPS:
         from . import ops_glenet
 
         return getattr(ops_glenet, name)
+    if name in _IOU3D_OPS:
+        from . import ops_iou3d
+
+        return getattr(ops_iou3d, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
