@@ -17,6 +17,9 @@ static inline int lc_launch_status() {
     return e == hipSuccess ? LC_OK : (int)e;
 }
 
+// what a kernel reads or writes as 128-bit quads
+static inline bool lc_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
 // Output stores of the streaming kernels (resampling, attention output, fp32 GroupNorm apply): write-THROUGH (sc1), like the
 // convolution epilogues (conv_f16x2_common.h epi_store / LC_DEF_AUX): lines left dirty in the per-XCD L2s are written back at
 // the kernel boundary, in front of the next launch; written through, they stream out while the kernel runs.  Clean same-box

@@ -422,8 +422,6 @@ __global__ __launch_bounds__(64) void gl_score_kernel(const float* __restrict__ 
     if (lane == 7) mean_overlap[b] = mean;
 }
 
-bool gl_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 }  // namespace
 
 extern "C" int lc_segment_center_fwd(const float* points, const int32_t* offsets, int B, int64_t total, double sx, double sy,
@@ -445,7 +443,7 @@ extern "C" int lc_glenet_trunk_fwd(const float* norm, int64_t total, const int32
         !sb3 || !featA || !featS || B < 1 || K < 1 || R < 1 || total < 1)
         return LC_EINVAL;
     if (total > (int64_t)0x7fffffff || R > (int64_t)0x7fffffff || K >= (1 << 24)) return LC_EUNSUP;
-    if (!gl_aligned16(w2) || !gl_aligned16(w3)) return LC_EUNSUP;      // their rows are read as 128-bit quads
+    if (!lc_aligned16(w2) || !lc_aligned16(w3)) return LC_EUNSUP;      // their rows are read as 128-bit quads
     hipLaunchKernelGGL(gl_trunk_kernel, dim3((unsigned)R), dim3(256), 0, lc_s(s), norm, (long long)total, offsets, choice, B, K,
                        (long long)R, w1, b1, w2, b2, w3, b3, sw1, sb1, sw2, sb2, sw3, sb3, featA, featS);
     return lc_launch_status();

@@ -21,12 +21,12 @@
 //       rows 0..d-1 alpha (x[idx] - x[anchor]) / (sigma_b + 1e-5) + beta, rows d..2d-1 x[anchor], columns s K + k.
 //       sigma_b (unbiased, over all S K d differences of cloud b) is a two-level sum in float64: one (sum, sum of squares)
 //       pair per block of 256 columns, then every apply block adds the pairs in the same order.
-//   pm_conv_kernel<CW>   y = act(W x + b (+ res)) on [B, C, L]: exact fp32 on v_mfma_f32_32x32x2_f32, the layout and the
-//       k chunking of rangenet.hip's 1x1 mode (chunks of 32 input channels summed from zero, then added in ascending
-//       order), a wave = 32 output channels x 64 columns.  The residual is added BEFORE the activation.
+//   PmGeom<CW> / PmEpi   y = act(W x + b (+ res)) on [B, C, L]: the dense tile engine of dense_f32.h (exact fp32 on
+//       v_mfma_f32_32x32x2_f32; the kernel, the packed weights and the k order are RangeNet's 1x1 mode: chunks of 32 input
+//       channels summed from zero, then added in ascending order) with the pointwise geometry, a wave = 32 output channels
+//       x 64 columns.  The residual is added BEFORE the activation.
 //   pm_groupmax_kernel   out[b, c, g] = max_k x[b, c, g K + k], out with caller-given strides.
-#include "common.h"
-#include "f16x2.h"      // mfma_row
+#include "dense_f32.h"
 
 namespace {
 
@@ -275,115 +275,34 @@ __global__ __launch_bounds__(GR_T) void pm_group_apply_kernel(const float* __res
 }
 
 // ---- dense layers ----------------------------------------------------------------------------------------------------
-constexpr int PM_KC = 32;                     // input channels per accumulation chunk
-constexpr int PM_CO = 32;                     // output channels per wave = MFMA rows
-constexpr int PM_TL = 64;                     // columns per wave: two MFMA column groups per weight register
+// the engine's pointwise geometry: 1x1, one row per block, a wave = 32 output channels x 64 columns = two MFMA column
+// groups per weight register (accumulator r reads LDS offset 32 r)
+template <int CW_>
+struct PmGeom {
+    static constexpr int KC = 32, T = 1, CW = CW_;
+    static constexpr int TH = 1, PXW = 2 * DF_TW;
+    static constexpr bool FLAT = true;
+    static constexpr int S = 1, PADH = 0, PADW = 0;
+    static constexpr int R = 2, NACC = 2;
+    static constexpr int PF_MAX_NLD = 32;
+    static constexpr int lds_off(int r, int, int) { return DF_TW * r; }
+    static constexpr int acc_of(int r, int) { return r; }
+    static constexpr int out_row(int) { return 0; }
+    __host__ __device__ static constexpr int out_col(int i, int px) { return px + DF_TW * i; }
+};
 
-struct PmArgs {
-    const float* x;
-    const float* wpk;
+struct PmEpi {
     const float* bias;
     const float* res;
     float* y;
-    int Ci, Co, L, act, co_groups;
+    int act;
+    __device__ __forceinline__ void operator()(int co, size_t o, float acc) const {
+        float val = acc + bias[co];
+        if (res) val += res[o];
+        if (act) val = val > 0.f ? val : 0.f;
+        y[o] = val;
+    }
 };
-
-template <int CW>
-__global__ __launch_bounds__(256, 2) void pm_conv_kernel(PmArgs a) {
-    constexpr int PG = 4 / CW, NCOL = PM_TL * PG;
-    // channel stride: odd modulo the 64 banks, so the two lane halves (channels 2 s, 2 s + 1) do not meet in every bank
-    constexpr int CS = NCOL + ((33 - NCOL % 64) + 64) % 64;
-    __shared__ float tile[PM_KC * CS];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int j = lane & 31, h = lane >> 5;
-    const int b = blockIdx.z / a.co_groups, cg = blockIdx.z - b * a.co_groups;
-    const int p0 = blockIdx.x * NCOL;
-    const int cb = cg * CW + wave % CW;       // block of 32 output channels
-    const int pg = wave / CW;
-    const bool live = cb * PM_CO < a.Co;
-    const int nchunk = (a.Ci + PM_KC - 1) / PM_KC;
-    const float* xb = a.x + (size_t)b * a.Ci * a.L;
-
-    f32x16 acc[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int v = 0; v < 16; ++v) acc[i][v] = 0.f;
-
-    // the next chunk's tile travels in registers while this chunk's products run
-    constexpr int NE = PM_KC * NCOL, NLD = NE / 256;
-    float stg[NLD];
-    auto fetch = [&](int chunk) {
-#pragma unroll
-        for (int i = 0; i < NLD; ++i) {
-            const int e = tid + 256 * i;
-            const int ch = e / NCOL, c = e - ch * NCOL;
-            const int gc = chunk * PM_KC + ch, gl = p0 + c;
-            stg[i] = (gc < a.Ci && gl < a.L) ? xb[(size_t)gc * a.L + gl] : 0.f;
-        }
-    };
-    fetch(0);
-    for (int chunk = 0; chunk < nchunk; ++chunk) {
-        if (chunk) __syncthreads();           // every wave has read the previous chunk
-#pragma unroll
-        for (int i = 0; i < NLD; ++i) {
-            const int e = tid + 256 * i;
-            const int ch = e / NCOL, c = e - ch * NCOL;
-            tile[ch * CS + c] = stg[i];
-        }
-        __syncthreads();
-        if (chunk + 1 < nchunk) fetch(chunk + 1);
-        if (live) {
-            f32x16 part[2];
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int v = 0; v < 16; ++v) part[i][v] = 0.f;
-            const f32x4* wp = reinterpret_cast<const f32x4*>(a.wpk) + ((size_t)cb * nchunk + chunk) * ((PM_KC / 8) * 64) + lane;
-            const float* bp = &tile[h * CS + pg * PM_TL + j];
-#pragma unroll
-            for (int q = 0; q < PM_KC / 8; ++q) {
-                const f32x4 w4 = wp[q * 64];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int s = 4 * q + e;
-#pragma unroll
-                    for (int r = 0; r < 2; ++r)
-                        part[r] = __builtin_amdgcn_mfma_f32_32x32x2f32(w4[e], bp[2 * s * CS + 32 * r], part[r], 0, 0, 0);
-                }
-            }
-#pragma unroll
-            for (int i = 0; i < 2; ++i) acc[i] += part[i];
-        }
-    }
-    if (!live) return;
-
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-        const int col = p0 + pg * PM_TL + 32 * r + j;
-        if (col >= a.L) continue;
-#pragma unroll
-        for (int v = 0; v < 16; ++v) {
-            const int co = mfma_row(v, h, cb * PM_CO);
-            if (co >= a.Co) continue;
-            const size_t o = ((size_t)b * a.Co + co) * a.L + col;
-            float val = acc[r][v] + a.bias[co];
-            if (a.res) val += a.res[o];
-            if (a.act) val = val > 0.f ? val : 0.f;
-            a.y[o] = val;
-        }
-    }
-}
-
-template <int CW>
-int pm_conv_launch(const PmArgs& a, int B, lc_stream_t s) {
-    constexpr int NCOL = PM_TL * (4 / CW);
-    const long long gx = ((long long)a.L + NCOL - 1) / NCOL, gz = (long long)B * a.co_groups;
-    if (gx > 2147483647ll || gz > 65535) return LC_EUNSUP;
-    hipLaunchKernelGGL((pm_conv_kernel<CW>), dim3((unsigned)gx, 1, (unsigned)gz), dim3(256), 0, lc_s(s), a);
-    return lc_launch_status();
-}
 
 // one thread per (b, c, g)
 __global__ __launch_bounds__(256) void pm_groupmax_kernel(const float* __restrict__ x, float* __restrict__ out, int C, int G,
@@ -400,8 +319,6 @@ __global__ __launch_bounds__(256) void pm_groupmax_kernel(const float* __restric
     out[b * obs + c * ocs + g * ogs] = m;
 }
 
-bool pm_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 }  // namespace
 
 extern "C" int lc_pointmlp_limit(int which) {
@@ -409,9 +326,9 @@ extern "C" int lc_pointmlp_limit(int which) {
         case 0: return LC_FPS_MAX_N;
         case 1: return LC_KNN_MAX_N;
         case 2: return LC_KNN_MAX_K;
-        case 3: return PM_KC;
-        case 4: return PM_CO;
-        case 5: return PM_TL;
+        case 3: return PmGeom<1>::KC;
+        case 4: return DF_CO;
+        case 5: return PmGeom<1>::PXW;
         case 6: return GR_T;
         default: return 0;
     }
@@ -471,23 +388,13 @@ extern "C" int lc_pointmlp_group_fwd(const float* x, const int* fps_idx, const i
 
 extern "C" int64_t lc_pointmlp_packed_weight_elems(int Ci, int Co) {
     if (Ci < 1 || Co < 1) return 0;
-    return (int64_t)((Co + PM_CO - 1) / PM_CO) * ((Ci + PM_KC - 1) / PM_KC) * PM_KC * PM_CO;
+    return df_packed_elems(PmGeom<1>::KC, 1, Ci, Co);
 }
 
-// HOST pointers.  w [Co][Ci].  out: [co block][chunk][KC / 8][lane][4]: entry e of lane l is the weight of output channel
-// 32 block + (l & 31), input channel 32 chunk + 2 (4 q + e) + (l >> 5); zeros past Ci and Co.
+// HOST pointers.  w [Co][Ci].  out: the engine's layout at one tap (dense_f32.h: df_pack_weight).
 extern "C" int lc_pointmlp_pack_weight(const float* w, int Ci, int Co, float* out) {
     if (!w || !out || Ci < 1 || Co < 1) return LC_EINVAL;
-    const int nchunk = (Ci + PM_KC - 1) / PM_KC, ncb = (Co + PM_CO - 1) / PM_CO;
-    size_t o = 0;
-    for (int cb = 0; cb < ncb; ++cb)
-        for (int ch = 0; ch < nchunk; ++ch)
-            for (int q = 0; q < PM_KC / 8; ++q)
-                for (int l = 0; l < 64; ++l)
-                    for (int e = 0; e < 4; ++e, ++o) {
-                        const int co = cb * PM_CO + (l & 31), ci = ch * PM_KC + 2 * (4 * q + e) + (l >> 5);
-                        out[o] = (co < Co && ci < Ci) ? w[(size_t)co * Ci + ci] : 0.f;
-                    }
+    df_pack_weight(PmGeom<1>::KC, 1, Ci, Co, out, [=](int co, int ci, int) { return w[(size_t)co * Ci + ci]; });
     return LC_OK;
 }
 
@@ -495,14 +402,8 @@ extern "C" int lc_pointmlp_conv_fwd(const float* x, const float* wpk, const floa
                                     int Ci, int Co, int L, int act, lc_stream_t s) {
     if (!x || !wpk || !bias || !y || B < 1 || Ci < 1 || Co < 1 || L < 1) return LC_EINVAL;
     if (y == x || y == res) return LC_EINVAL;                     // a block reads columns other blocks write
-    if (!pm_aligned16(wpk)) return LC_EUNSUP;                     // read as 128-bit quads
-    PmArgs a{x, wpk, bias, res, y, Ci, Co, L, act ? 1 : 0, 1};
-    // narrow layers give their waves to more columns instead of idle channel blocks
-    const int cw = Co <= 32 ? 1 : (Co <= 64 ? 2 : 4);
-    a.co_groups = ((Co + PM_CO - 1) / PM_CO + cw - 1) / cw;
-    if (cw == 1) return pm_conv_launch<1>(a, B, s);
-    if (cw == 2) return pm_conv_launch<2>(a, B, s);
-    return pm_conv_launch<4>(a, B, s);
+    if (!lc_aligned16(wpk)) return LC_EUNSUP;                     // read as 128-bit quads
+    return df_dispatch<PmGeom>(DfArgs{x, wpk, Ci, Co, 1, L, L, 1}, PmEpi{bias, res, y, act ? 1 : 0}, B, L, s);
 }
 
 extern "C" int lc_pointmlp_groupmax_fwd(const float* x, float* out, int B, int C, int G, int K, int64_t out_bs, int64_t out_cs,

@@ -96,8 +96,6 @@ __global__ __launch_bounds__(256) void pn_reduce_kernel(const float* __restrict_
     }
 }
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 }  // namespace
 
 extern "C" int64_t lc_pointnet_trunk_scratch_elems(int B, int N) {
@@ -111,7 +109,7 @@ extern "C" int lc_pointnet_trunk_fwd(const float* x, int64_t x_bs, const float* 
     if (!x || !w1 || !b1 || !w2 || !b2 || !w3 || !b3 || !y || !scratch || B < 1 || N < 1) return LC_EINVAL;
     if (B > 65535 || N >= (1 << 24)) return LC_EUNSUP;
     if (x_bs < 3ll * N || y_bs < PN_C3) return LC_EUNSUP;
-    if (!aligned16(w2) || !aligned16(w3)) return LC_EUNSUP;      // their rows are read as 128-bit quads
+    if (!lc_aligned16(w2) || !lc_aligned16(w3)) return LC_EUNSUP;      // their rows are read as 128-bit quads
     const int tiles = (N + PN_T - 1) / PN_T;
     hipLaunchKernelGGL(pn_trunk_kernel, dim3(tiles, B), dim3(256), 0, lc_s(s), x, (long long)x_bs, trans, w1, b1, w2, b2,
                        w3, N, tiles, scratch);

@@ -286,8 +286,6 @@ __global__ __launch_bounds__(256) void sp_sector_kernel(const float* __restrict_
     }
 }
 
-bool sp_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 bool sp_width_in(int c) { return c == 4 || c == 16 || c == 32 || c == 48 || c == 64 || c == 96 || c == 128 || c == 192; }
 bool sp_width_out(int c) { return c == 16 || c == 32 || c == 48 || c == 64 || c == 128; }
 
@@ -336,7 +334,7 @@ extern "C" int lc_spconv_fwd(const float* x, int64_t ldx, const int32_t* nbr, in
     if (M > LC_SPCONV_MAX_ROWS || n_in > LC_SPCONV_MAX_ROWS) return LC_EUNSUP;
     if (ldx < Ci || ldy < (int64_t)y_col + Co || (res && ldr < Co)) return LC_EINVAL;
     if ((ldx & 3) || (ldy & 3) || (y_col & 3) || (res && (ldr & 3))) return LC_EUNSUP;   // rows are read and written as quads
-    if (!sp_aligned16(x) || !sp_aligned16(w) || !sp_aligned16(y) || (b && !sp_aligned16(b)) || (res && !sp_aligned16(res)))
+    if (!lc_aligned16(x) || !lc_aligned16(w) || !lc_aligned16(y) || (b && !lc_aligned16(b)) || (res && !lc_aligned16(res)))
         return LC_EUNSUP;
     float* yo = y + y_col;
     const dim3 grid((M + SP_T - 1) / SP_T), block(256);

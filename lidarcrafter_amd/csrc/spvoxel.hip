@@ -157,8 +157,6 @@ __global__ __launch_bounds__(64) void spv_vox_kernel(const float* __restrict__ f
     out[(size_t)v * ldo + c] = acc;
 }
 
-bool spv_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 }  // namespace
 
 extern "C" int lc_spvox_query(const float* pts, int N, int stride, const void* table, int n_table, int32_t* idx, float* w,
@@ -166,7 +164,7 @@ extern "C" int lc_spvox_query(const float* pts, int N, int stride, const void* t
     if (!pts || !table || !idx || N < 1 || n_table < 1 || stride < 1) return LC_EINVAL;
     if (N > LC_SPCONV_MAX_ROWS || n_table > LC_SPCONV_MAX_ROWS || stride > LC_SPCONV_MAX_STRIDE) return LC_EUNSUP;
     if (stride & (stride - 1)) return LC_EUNSUP;                       // floor(p / s) * s is exact for a power of two only
-    if (!spv_aligned16(pts) || !spv_aligned16(idx) || (w && !spv_aligned16(w))) return LC_EUNSUP;
+    if (!lc_aligned16(pts) || !lc_aligned16(idx) || (w && !lc_aligned16(w))) return LC_EUNSUP;
     const unsigned cap = sp_capacity(n_table);
     const unsigned long long* keys = static_cast<const unsigned long long*>(table);
     const int32_t* vals = reinterpret_cast<const int32_t*>(keys + cap);
@@ -184,7 +182,7 @@ extern "C" int lc_spvox_devoxelize(const float* f, int64_t ldf, int n_rows, cons
     if (N > LC_SPCONV_MAX_ROWS || n_rows > LC_SPCONV_MAX_ROWS) return LC_EUNSUP;
     if (ldf < C || ldo < C || (addend && lda < C)) return LC_EINVAL;
     if ((ldf & 3) || (ldo & 3) || (addend && (lda & 3))) return LC_EUNSUP;                  // rows are read and written as quads
-    if (!spv_aligned16(f) || !spv_aligned16(out) || (addend && !spv_aligned16(addend))) return LC_EUNSUP;
+    if (!lc_aligned16(f) || !lc_aligned16(out) || (addend && !lc_aligned16(addend))) return LC_EUNSUP;
 #define SPV_DEVOX(LPP)                                                                                               \
     hipLaunchKernelGGL(spv_devox_kernel<LPP>, dim3((unsigned)((N + (256 / LPP) - 1) / (256 / LPP))), dim3(256), 0,  \
                        lc_s(s), f, (long long)ldf, n_rows, idx, w, addend, (long long)lda, out, (long long)ldo, N)

@@ -22,7 +22,8 @@ def limit(which: str) -> int:
 
 
 def conv_block_cols(Co: int) -> int:
-    """Columns per block of pm_conv_kernel for a layer of Co output channels (256 for Co <= 32, 128 for Co <= 64, else 64)."""
+    """Columns per block of the pointwise geometry (csrc/pointmlp.hip: PmGeom) for a layer of Co output channels (256 for
+    Co <= 32, 128 for Co <= 64, else 64)."""
     return limit("tile_l") * (4 if Co <= 32 else (2 if Co <= 64 else 1))
 
 
@@ -123,7 +124,8 @@ def packed_weight_elems(Ci: int, Co: int) -> int:
 
 
 def pack_weight(w: torch.Tensor) -> torch.Tensor:
-    """Host: a float32 CPU weight [Co,Ci] -> the float32 CPU vector pm_conv_kernel reads."""
+    """Host: a float32 CPU weight [Co,Ci] -> the float32 CPU vector df_conv_kernel (csrc/dense_f32.h) reads:
+    ops_rangenet.pack_weight's at one tap."""
     if w.is_cuda or w.dtype != _F32 or w.dim() != 2 or w.numel() == 0:
         raise ValueError("pack_weight: a non-empty float32 CPU tensor [Co,Ci]")
     Co, Ci = w.shape

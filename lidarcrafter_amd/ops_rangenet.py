@@ -11,7 +11,8 @@ import torch
 from ._lib import check, lib
 from .ops import _F32, _entry, _req, _stream
 
-# tile extents of rn_conv_kernel (tests/test_rangenet_host.py compares them with lc_rangenet_tile_extent)
+# tile extents of RangeNet's geometries of df_conv_kernel (csrc/dense_f32.h; tests/test_rangenet_host.py compares them with
+# lc_rangenet_tile_extent)
 TILE_W = 32          # pixels per wave: a block row is TILE_W * 4 / CW pixels, CW = 1 (Co <= 32), 2 (Co <= 64) or 4
 TILE_H = 2           # output rows per block
 TILE_CO = 32         # output channels per wave
@@ -51,7 +52,7 @@ def packed_weight_elems(mode: int, Ci: int, Co: int) -> int:
 
 
 def pack_weight(w: torch.Tensor, mode: int) -> torch.Tensor:
-    """Host: a float32 CPU weight in torch layout -> the float32 CPU vector rn_conv_kernel reads."""
+    """Host: a float32 CPU weight in torch layout -> the float32 CPU vector df_conv_kernel (csrc/dense_f32.h) reads."""
     if w.is_cuda or w.dtype != _F32 or w.dim() != 4:
         raise ValueError("pack_weight: a float32 CPU tensor [Co,Ci,k,k] (mode 3: [Ci,Co,1,4])")
     Ci, Co = (w.shape[0], w.shape[1]) if mode == 3 else (w.shape[1], w.shape[0])

@@ -221,6 +221,23 @@ def test_conv_bits_and_aliasing(dev):
         KM.conv(sq, w2[:-4], b.to(dev), 80, True)
 
 
+@pytest.mark.parametrize("res", [False, True], ids=["plain", "residual"])
+@pytest.mark.parametrize("Ci,Co", [(3, 20), (33, 65), (64, 32)])
+def test_conv_bits_equal_rangenet_1x1(dev, Ci, Co, res):
+    """The pointwise layer and RangeNet's 1x1 mode are two geometries of one engine (csrc/dense_f32.h): the same packed
+    weights, the same chunks, the same k order; without an activation the epilogues are the same arithmetic (+ bias, + one
+    addend).  So the bits are equal, whatever the tile: L = 1, 33, 257 as one image row, and L = 66 as two rows of 33."""
+    from lidarcrafter_amd import ops_rangenet as KR
+
+    for i, (L, H) in enumerate(((1, 1), (33, 1), (257, 1), (66, 2))):
+        x, w, b, r = _dense_case(2, Ci, Co, L, 7 * Ci + Co + i, res)
+        x, b, r = x.to(dev), b.to(dev), None if r is None else r.to(dev)
+        got = KM.conv(x, KM.pack_weight(w).to(dev), b, Co, False, res=r)
+        want = KR.conv(x.view(2, Ci, H, L // H), KR.pack_weight(w[:, :, None, None].contiguous(), 0).to(dev), b, 0, Co, False,
+                       res1=None if r is None else r.view(2, Co, H, L // H))
+        assert torch.equal(got, want.view(2, Co, L)), (Ci, Co, L, H, res)
+
+
 @pytest.mark.parametrize("C,G,K", [(7, 5, 24), (33, 11, 24), (4, 1, 64), (3, 300, 4)])
 def test_groupmax(dev, C, G, K):
     """G K = 120, 264, 64, 1200: the last group ends inside a dense tile; G = 1: the global pool."""

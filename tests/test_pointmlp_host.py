@@ -282,6 +282,16 @@ def test_cgf_and_dcf_against_the_fixture(golden, capsys):
     assert "Average confidence per class:" in capsys.readouterr().out
 
 
+@pytest.mark.parametrize("Co,Ci", [(1, 1), (20, 3), (32, 32), (33, 65), (65, 33)])
+def test_packed_weights_are_rangenet_1x1s(Co, Ci):
+    """One packed-weight layout (csrc/dense_f32.h): the pointwise packer is RangeNet's at one tap and chunks of 32."""
+    from lidarcrafter_amd import ops_pointmlp as KM, ops_rangenet as KR
+
+    w = torch.randn(Co, Ci, generator=torch.Generator().manual_seed(100 * Co + Ci))
+    assert KM.packed_weight_elems(Ci, Co) == KR.packed_weight_elems(0, Ci, Co)
+    assert torch.equal(KM.pack_weight(w), KR.pack_weight(w[:, :, None, None], 0))
+
+
 # ---- what the GPU bound can see ----------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", ["tiny", "elite"])
 def test_mutations_move_the_features_by_16_bounds(golden, name):
