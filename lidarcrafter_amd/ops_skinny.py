@@ -110,6 +110,8 @@ def rowprep(segs: Sequence, M: int, groups: int = 0, eps: float = 1e-5, gamma=No
             out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Per-row GroupNorm over `groups` groups (1: LayerNorm; 0: none) [+ SiLU] of the gathered concatenation of `segs`."""
     arr, Cn = segments(segs, M)
+    if beta is not None and gamma is None:
+        raise ValueError("rowprep: beta without gamma (the kernel applies beta only next to gamma)")
     dev = segs[0][0].device
     if out is None:
         out = torch.empty((M, Cn), device=dev, dtype=_F32)
