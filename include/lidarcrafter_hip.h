@@ -1152,6 +1152,9 @@ int lc_rangenet_reduce_fwd(const float* x, float* out, int B, int C, int H, int 
 #define LC_KNN_MAX_K 32
 int lc_pointmlp_limit(int which);
 int lc_fps_fwd(const float* xyz, int* idx, int B, int N, int M, lc_stream_t s);
+/* one cloud xyz [N,3] of a stacked batch: the same kernel with the tie rule of a 1024-thread block whatever N is (the
+ * reference's stack_farthest_point_sampling_kernel; lc_fps_fwd's rule for N >= 1024), idx [M] = the picks + off. */
+int lc_fps_stack_fwd(const float* xyz, int* idx, int N, int M, int off, lc_stream_t s);
 int lc_knn_fwd(const float* xyz, const int* query_idx, int* out, int B, int N, int S, int K, lc_stream_t s);
 int64_t lc_pointmlp_group_scratch_elems(int B, int S, int K);
 int lc_pointmlp_group_fwd(const float* x, const int* fps_idx, const int* knn_idx, const float* alpha, const float* beta,
@@ -1270,6 +1273,55 @@ int lc_nms_mask_fwd(const float* boxes, int n, float thresh, int normal, uint64_
 int lc_nms_select_fwd(const uint64_t* mask, int n, int64_t* keep, int32_t* count, lc_stream_t s);
 int lc_boxes_iou_bev_host(const float* boxes_a, int na, const float* boxes_b, int nb, float* out);
 int lc_boxes_overlap_bev_host(const float* boxes_a, int na, const float* boxes_b, int nb, float* out, int32_t* cnt);
+
+/* ---------------------------------------------------------------------------------------------
+ * lidargen.ops.pointnet2.pointnet2_stack (csrc/pointnet2_stack.hip): the ragged-batch set-abstraction
+ * operators.  Contiguous float32 / int32 DEVICE tensors; a stacked tensor holds cloud b in rows start_b .. start_b + n_b - 1,
+ * the counts [B] are device memory.  Every entry checks its arguments before any launch (null pointers, negative sizes:
+ * LC_EINVAL; B > LC_PN2_MAX_BATCH, nsample > LC_PN2_MAX_NSAMPLE, sizes past the 32-bit index range: LC_EUNSUP); a row count
+ * of 0 on the output side returns LC_OK with nothing launched.  The offsets are one exclusive scan per call (clamped into
+ * the tensors, so counts that do not add up to the row counts leave rows empty, never an access outside an operand); every
+ * index is checked against its own cloud before it is dereferenced.  No float atomics, fixed summation orders, a cloud's bits
+ * do not depend on the batch.  Distances: d = (dx dx + dy dy) + dz dz in float32, each operation rounded on its own.
+ * scratch: lc_pn2_scratch_elems(B, rows of the query side) int32, written before it is read by the same call.
+ *   lc_pn2_ball_query_fwd: idx [M, nsample] = the first nsample points (ascending, local indices) of the centre's cloud with
+ *     d < radius * radius (float32 product, strict), the rest of the row the first hit; an empty ball is [-1, 0, ...].
+ *   lc_pn2_group_fwd: out [M, C, nsample], out[m, c, s] = features[start + idx[m, s], c], 0 for an index outside [0, n_b).
+ *     (No backward entry.)
+ *   lc_pn2_three_nn_fwd: unknown [N, 3], known [M, 3] -> dist2 [N, 3], idx [N, 3] (global rows), ascending (distance,
+ *     index) under strict <; a slot never filled holds +inf and the cloud's start row.
+ *   lc_pn2_three_interpolate_fwd: out [N, C] = (w0 f0 + w1 f1) + w2 f2, features [M, C]; an index outside [0, M) adds 0.
+ *   lc_pn2_three_interpolate_bwd: grad_features [M, C]: row m = the sum of grad_out[n, c] weight[n, j] over the entries
+ *     e = 3 n + j in order[seg[m] .. seg[m + 1]), in that order (order: the stable sort of the flat indices, seg [M + 1]
+ *     the first position of every row).
+ *   lc_pn2_voxel_query_fwd: new_coords [M, 4] = (batch, z, y, x), point_indices [B, Z, Y, X] (global rows of xyz [N, 3] or
+ *     -1): the (dz, dy, dx)-ascending walk over the cells within the ranges, d <= radius * radius (inclusive), the first
+ *     nsample hits, the row pre-filled with the first; an empty row is [-1, 0, ...].  Ranges <= 1024.
+ *   lc_pn2_sa_first_fwd: y [Co, M nsample] = relu(W G + bias), G the grouped operand of QueryAndGroup (rows 0..2
+ *     xyz[start + idx] - new_xyz[m] when use_xyz, then features [N, C]; C may be 0 with use_xyz; a column of an empty ball,
+ *     idx[m, 0] < 0, is zero) gathered into the dense engine's tile: wpk = lc_pointmlp_pack_weight of W [Co, C + 3 use_xyz],
+ *     16-byte aligned; the bits of lc_pointmlp_conv_fwd (act = 1, no residual) on the materialised operand.
+ *   lc_pn2_limit(i): 0 LC_PN2_MAX_NSAMPLE, 1 LC_PN2_MAX_BATCH, 2 the columns per block of the gathered layer at Co <= 32. */
+#define LC_PN2_MAX_NSAMPLE 256
+#define LC_PN2_MAX_BATCH 4096
+int lc_pn2_limit(int which);
+int64_t lc_pn2_scratch_elems(int B, int M);
+int lc_pn2_ball_query_fwd(const float* xyz, const int* xyz_cnt, const float* new_xyz, const int* new_cnt, int* idx,
+                          int* scratch, int B, int N, int M, float radius, int nsample, lc_stream_t s);
+int lc_pn2_group_fwd(const float* features, const int* features_cnt, const int* idx, const int* idx_cnt, float* out,
+                     int* scratch, int B, int N, int C, int M, int nsample, lc_stream_t s);
+int lc_pn2_three_nn_fwd(const float* unknown, const int* unknown_cnt, const float* known, const int* known_cnt, float* dist2,
+                        int* idx, int* scratch, int B, int N, int M, lc_stream_t s);
+int lc_pn2_three_interpolate_fwd(const float* features, const int* idx, const float* weight, float* out, int N, int C, int M,
+                                 lc_stream_t s);
+int lc_pn2_three_interpolate_bwd(const float* grad_out, const int* order, const int* seg, const float* weight,
+                                 float* grad_features, int N, int C, int M, lc_stream_t s);
+int lc_pn2_voxel_query_fwd(const float* new_xyz, const float* xyz, const int* new_coords, const int* point_indices, int* idx,
+                           int M, int N, int B, int Z, int Y, int X, int nsample, float radius, int z_range, int y_range,
+                           int x_range, lc_stream_t s);
+int lc_pn2_sa_first_fwd(const float* xyz, const int* xyz_cnt, const float* new_xyz, const int* new_cnt, const float* features,
+                        const int* idx, const float* wpk, const float* bias, float* y, int* scratch, int B, int N, int M, int C,
+                        int Co, int nsample, int use_xyz, lc_stream_t s);
 
 #ifdef __cplusplus
 }

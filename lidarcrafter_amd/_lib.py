@@ -220,6 +220,7 @@ SIGNATURES = {
     "lc_rangenet_reduce_fwd": (i32, [vp, vp, i32, i32, i32, i32, i32, vp]),
     "lc_pointmlp_limit": (i32, [i32]),
     "lc_fps_fwd": (i32, [vp, vp, i32, i32, i32, vp]),
+    "lc_fps_stack_fwd": (i32, [vp, vp, i32, i32, i32, vp]),
     "lc_knn_fwd": (i32, [vp, vp, vp, i32, i32, i32, i32, vp]),
     "lc_pointmlp_group_scratch_elems": (i64, [i32, i32, i32]),
     "lc_pointmlp_group_fwd": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
@@ -243,6 +244,15 @@ SIGNATURES = {
     "lc_nms_select_fwd": (i32, [vp, i32, vp, vp, vp]),
     "lc_boxes_iou_bev_host": (i32, [vp, i32, vp, i32, vp]),
     "lc_boxes_overlap_bev_host": (i32, [vp, i32, vp, i32, vp, vp]),
+    "lc_pn2_limit": (i32, [i32]),
+    "lc_pn2_scratch_elems": (i64, [i32, i32]),
+    "lc_pn2_ball_query_fwd": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, i32, vp]),
+    "lc_pn2_group_fwd": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
+    "lc_pn2_three_nn_fwd": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
+    "lc_pn2_three_interpolate_fwd": (i32, [vp, vp, vp, vp, i32, i32, i32, vp]),
+    "lc_pn2_three_interpolate_bwd": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, vp]),
+    "lc_pn2_voxel_query_fwd": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, i32, i32, i32, vp]),
+    "lc_pn2_sa_first_fwd": (i32, [vp] * 10 + [i32] * 7 + [vp]),
 }
 
 _lib = None

@@ -67,7 +67,7 @@ constexpr int FPS_LDS_N = 4096;               // clouds up to here keep a copy o
 
 template <int P, bool LDSXYZ>
 __global__ __launch_bounds__(FPS_T) void pm_fps_kernel(const float* __restrict__ xyz, int* __restrict__ idx, int N, int M,
-                                                       int bs_log2) {
+                                                       int bs_log2, int off) {
     __shared__ float sx[LDSXYZ ? 3 * FPS_LDS_N : 3];
     __shared__ pm_u64 slot[2][FPS_T / 64];
     const int tid = threadIdx.x, T = blockDim.x, lane = tid & 63;
@@ -94,7 +94,7 @@ __global__ __launch_bounds__(FPS_T) void pm_fps_kernel(const float* __restrict__
             sx[3 * k + 2] = pz[i];
         }
     }
-    if (tid == 0) out[0] = 0;
+    if (tid == 0) out[0] = off;
     if (LDSXYZ) __syncthreads();
 
     int old = 0;
@@ -122,14 +122,27 @@ __global__ __launch_bounds__(FPS_T) void pm_fps_kernel(const float* __restrict__
         }
         const unsigned tie = ~(unsigned)best;
         old = (int)(pm_rev(tie >> 4, bs_log2) + ((tie & 15u) << bs_log2));
-        if (tid == 0) out[j] = old;
+        if (tid == 0) out[j] = old + off;
     }
 }
 
 template <int P, bool LDSXYZ>
-int pm_fps_launch(const float* xyz, int* idx, int B, int N, int M, int T, int bs_log2, lc_stream_t s) {
-    hipLaunchKernelGGL((pm_fps_kernel<P, LDSXYZ>), dim3((unsigned)B), dim3((unsigned)T), 0, lc_s(s), xyz, idx, N, M, bs_log2);
+int pm_fps_launch(const float* xyz, int* idx, int B, int N, int M, int T, int bs_log2, int off, lc_stream_t s) {
+    hipLaunchKernelGGL((pm_fps_kernel<P, LDSXYZ>), dim3((unsigned)B), dim3((unsigned)T), 0, lc_s(s), xyz, idx, N, M, bs_log2,
+                       off);
     return lc_launch_status();
+}
+
+// bs_log2: the block of the tie rule; off: added to every index written
+int pm_fps_dispatch(const float* xyz, int* idx, int B, int N, int M, int bs_log2, int off, lc_stream_t s) {
+    const int T = N >= FPS_T ? FPS_T : (N + 63) / 64 * 64;
+    const int per = (N + T - 1) / T;
+    if (N > FPS_LDS_N) return pm_fps_launch<32, false>(xyz, idx, B, N, M, T, bs_log2, off, s);
+    if (per <= 1) return pm_fps_launch<1, true>(xyz, idx, B, N, M, T, bs_log2, off, s);
+    if (per <= 2) return pm_fps_launch<2, true>(xyz, idx, B, N, M, T, bs_log2, off, s);
+    if (per <= 4) return pm_fps_launch<4, true>(xyz, idx, B, N, M, T, bs_log2, off, s);
+    if (per <= 8) return pm_fps_launch<8, true>(xyz, idx, B, N, M, T, bs_log2, off, s);
+    return pm_fps_launch<16, true>(xyz, idx, B, N, M, T, bs_log2, off, s);
 }
 
 // ---- k nearest neighbours --------------------------------------------------------------------------------------------
@@ -339,14 +352,15 @@ extern "C" int lc_fps_fwd(const float* xyz, int* idx, int B, int N, int M, lc_st
     if (N > LC_FPS_MAX_N) return LC_EUNSUP;
     int bs_log2 = 0;                          // the reference's block: the largest power of two <= min(N, 1024)
     while (bs_log2 < 10 && (2 << bs_log2) <= N) ++bs_log2;
-    const int T = N >= FPS_T ? FPS_T : (N + 63) / 64 * 64;
-    const int per = (N + T - 1) / T;
-    if (N > FPS_LDS_N) return pm_fps_launch<32, false>(xyz, idx, B, N, M, T, bs_log2, s);
-    if (per <= 1) return pm_fps_launch<1, true>(xyz, idx, B, N, M, T, bs_log2, s);
-    if (per <= 2) return pm_fps_launch<2, true>(xyz, idx, B, N, M, T, bs_log2, s);
-    if (per <= 4) return pm_fps_launch<4, true>(xyz, idx, B, N, M, T, bs_log2, s);
-    if (per <= 8) return pm_fps_launch<8, true>(xyz, idx, B, N, M, T, bs_log2, s);
-    return pm_fps_launch<16, true>(xyz, idx, B, N, M, T, bs_log2, s);
+    return pm_fps_dispatch(xyz, idx, B, N, M, bs_log2, 0, s);
+}
+
+// one cloud of a stacked batch (lidargen.ops.pointnet2.pointnet2_stack): the tie rule of a 1024-thread block whatever N
+// is, indices + off
+extern "C" int lc_fps_stack_fwd(const float* xyz, int* idx, int N, int M, int off, lc_stream_t s) {
+    if (!xyz || !idx || N < 1 || M < 1 || off < 0) return LC_EINVAL;
+    if (N > LC_FPS_MAX_N) return LC_EUNSUP;
+    return pm_fps_dispatch(xyz, idx, 1, N, M, 10, off, s);
 }
 
 extern "C" int lc_knn_fwd(const float* xyz, const int* query_idx, int* out, int B, int N, int S, int K, lc_stream_t s) {
