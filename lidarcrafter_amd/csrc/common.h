@@ -108,6 +108,16 @@ __device__ __forceinline__ float lc_wave_sum(float v) {
     return v;
 }
 
+// The squared distance of the point kernels (FPS, kNN, ball query, three-NN, voxel query), the references' expression
+// operation for operation: three differences, three products, two additions, each rounded (contraction off).
+__device__ __forceinline__ float lc_dist2(float x2, float y2, float z2, float x1, float y1, float z1) {
+#pragma clang fp contract(off)
+    const float dx = x2 - x1, dy = y2 - y1, dz = z2 - z1;
+    const float xx = dx * dx, yy = dy * dy, zz = dz * dz;
+    const float s = xx + yy;
+    return s + zz;
+}
+
 // max |.| of a block -> *slot (a float seen as its bit pattern; non-negative floats order like unsigned).  One atomicMax
 // per BLOCK, and only when the block's maximum beats what is already published (thousands of same-address atomics
 // serialise in L2: 150 us per call in the first version).  NaN / 0 never win.  Every thread of the block must call it.

@@ -4,7 +4,7 @@
 //
 //   pm_fps_kernel<P, LDSXYZ>   farthest point sampling, one block (at most 256 threads) per cloud, P points per thread in
 //       registers (coordinates + running distance).  Per pick: d = (dx dx + dy dy) + dz dz with separately rounded
-//       operations (pm_dist: contraction off), running distance = min(d, running), then ONE maximum of a packed 64-bit word
+//       operations (common.h lc_dist2: contraction off), running distance = min(d, running), then ONE maximum of a packed 64-bit word
 //       (distance bits << 32 | ~tie) through the wave (6 exchanges) and, in blocks of more than one wave, one barrier: the
 //       wave maxima go through a double-buffered LDS slot, so the slot of pick j is not written again before every wave has
 //       passed the barrier of pick j + 1.  The winner's coordinates are read from an LDS copy of the cloud (N <= 4096) or
@@ -21,23 +21,15 @@
 //       rows 0..d-1 alpha (x[idx] - x[anchor]) / (sigma_b + 1e-5) + beta, rows d..2d-1 x[anchor], columns s K + k.
 //       sigma_b (unbiased, over all S K d differences of cloud b) is a two-level sum in float64: one (sum, sum of squares)
 //       pair per block of 256 columns, then every apply block adds the pairs in the same order.
-//   PmGeom<CW> / PmEpi   y = act(W x + b (+ res)) on [B, C, L]: the dense tile engine of dense_f32.h (exact fp32 on
+//   lc_pointmlp_conv_fwd   y = act(W x + b (+ res)) on [B, C, L]: the dense tile engine of dense_f32.h (exact fp32 on
 //       v_mfma_f32_32x32x2_f32; the kernel, the packed weights and the k order are RangeNet's 1x1 mode: chunks of 32 input
-//       channels summed from zero, then added in ascending order) with the pointwise geometry, a wave = 32 output channels
-//       x 64 columns.  The residual is added BEFORE the activation.
+//       channels summed from zero, then added in ascending order) with the pointwise geometry and epilogue of
+//       dense_pointwise.h (PwGeom<CW> / PwEpi), a wave = 32 output channels x 64 columns.  The residual is added BEFORE
+//       the activation.  No kernel of this family is defined here.
 //   pm_groupmax_kernel   out[b, c, g] = max_k x[b, c, g K + k], out with caller-given strides.
-#include "dense_f32.h"
+#include "dense_pointwise.h"
 
 namespace {
-
-// the reference's distance, operation for operation: three differences, three products, two additions, each rounded
-__device__ __forceinline__ float pm_dist(float x2, float y2, float z2, float x1, float y1, float z1) {
-#pragma clang fp contract(off)
-    const float dx = x2 - x1, dy = y2 - y1, dz = z2 - z1;
-    const float xx = dx * dx, yy = dy * dy, zz = dz * dz;
-    const float s = xx + yy;
-    return s + zz;
-}
 
 typedef unsigned long long pm_u64;
 
@@ -105,7 +97,7 @@ __global__ __launch_bounds__(FPS_T) void pm_fps_kernel(const float* __restrict__
         pm_u64 best = 0;
 #pragma unroll
         for (int i = 0; i < P; ++i) {
-            const float d2 = fminf(pm_dist(px[i], py[i], pz[i], x1, y1, z1), run[i]);
+            const float d2 = fminf(lc_dist2(px[i], py[i], pz[i], x1, y1, z1), run[i]);
             run[i] = d2;
             const pm_u64 pk = ((pm_u64)__float_as_uint(d2) << 32) | key[i];
             best = pk > best ? pk : best;
@@ -149,7 +141,7 @@ int pm_fps_dispatch(const float* xyz, int* idx, int B, int N, int M, int bs_log2
 constexpr int KNN_REG_N = 1024;               // clouds up to here keep their packed words in registers
 
 __device__ __forceinline__ pm_u64 pm_knn_word(const float* p, int k, float qx, float qy, float qz) {
-    return ((pm_u64)__float_as_uint(pm_dist(p[3 * k], p[3 * k + 1], p[3 * k + 2], qx, qy, qz)) << 32) | (unsigned)k;
+    return ((pm_u64)__float_as_uint(lc_dist2(p[3 * k], p[3 * k + 1], p[3 * k + 2], qx, qy, qz)) << 32) | (unsigned)k;
 }
 
 // NPL > 0: N <= 64 NPL, the words of lane l are those of points l, l + 64, ...; NPL == 0: streamed
@@ -287,36 +279,7 @@ __global__ __launch_bounds__(GR_T) void pm_group_apply_kernel(const float* __res
     }
 }
 
-// ---- dense layers ----------------------------------------------------------------------------------------------------
-// the engine's pointwise geometry: 1x1, one row per block, a wave = 32 output channels x 64 columns = two MFMA column
-// groups per weight register (accumulator r reads LDS offset 32 r)
-template <int CW_>
-struct PmGeom {
-    static constexpr int KC = 32, T = 1, CW = CW_;
-    static constexpr int TH = 1, PXW = 2 * DF_TW;
-    static constexpr bool FLAT = true;
-    static constexpr int S = 1, PADH = 0, PADW = 0;
-    static constexpr int R = 2, NACC = 2;
-    static constexpr int PF_MAX_NLD = 32;
-    static constexpr int lds_off(int r, int, int) { return DF_TW * r; }
-    static constexpr int acc_of(int r, int) { return r; }
-    static constexpr int out_row(int) { return 0; }
-    __host__ __device__ static constexpr int out_col(int i, int px) { return px + DF_TW * i; }
-};
-
-struct PmEpi {
-    const float* bias;
-    const float* res;
-    float* y;
-    int act;
-    __device__ __forceinline__ void operator()(int co, size_t o, float acc) const {
-        float val = acc + bias[co];
-        if (res) val += res[o];
-        if (act) val = val > 0.f ? val : 0.f;
-        y[o] = val;
-    }
-};
-
+// ---- maximum over groups ---------------------------------------------------------------------------------------------
 // one thread per (b, c, g)
 __global__ __launch_bounds__(256) void pm_groupmax_kernel(const float* __restrict__ x, float* __restrict__ out, int C, int G,
                                                           int K, long long n, long long obs, long long ocs, long long ogs) {
@@ -339,9 +302,9 @@ extern "C" int lc_pointmlp_limit(int which) {
         case 0: return LC_FPS_MAX_N;
         case 1: return LC_KNN_MAX_N;
         case 2: return LC_KNN_MAX_K;
-        case 3: return PmGeom<1>::KC;
+        case 3: return PwGeom<1>::KC;
         case 4: return DF_CO;
-        case 5: return PmGeom<1>::PXW;
+        case 5: return PwGeom<1>::PXW;
         case 6: return GR_T;
         default: return 0;
     }
@@ -402,13 +365,13 @@ extern "C" int lc_pointmlp_group_fwd(const float* x, const int* fps_idx, const i
 
 extern "C" int64_t lc_pointmlp_packed_weight_elems(int Ci, int Co) {
     if (Ci < 1 || Co < 1) return 0;
-    return df_packed_elems(PmGeom<1>::KC, 1, Ci, Co);
+    return df_packed_elems(PwGeom<1>::KC, 1, Ci, Co);
 }
 
 // HOST pointers.  w [Co][Ci].  out: the engine's layout at one tap (dense_f32.h: df_pack_weight).
 extern "C" int lc_pointmlp_pack_weight(const float* w, int Ci, int Co, float* out) {
     if (!w || !out || Ci < 1 || Co < 1) return LC_EINVAL;
-    df_pack_weight(PmGeom<1>::KC, 1, Ci, Co, out, [=](int co, int ci, int) { return w[(size_t)co * Ci + ci]; });
+    df_pack_weight(PwGeom<1>::KC, 1, Ci, Co, out, [=](int co, int ci, int) { return w[(size_t)co * Ci + ci]; });
     return LC_OK;
 }
 
@@ -417,7 +380,7 @@ extern "C" int lc_pointmlp_conv_fwd(const float* x, const float* wpk, const floa
     if (!x || !wpk || !bias || !y || B < 1 || Ci < 1 || Co < 1 || L < 1) return LC_EINVAL;
     if (y == x || y == res) return LC_EINVAL;                     // a block reads columns other blocks write
     if (!lc_aligned16(wpk)) return LC_EUNSUP;                     // read as 128-bit quads
-    return df_dispatch<PmGeom>(DfArgs{x, wpk, Ci, Co, 1, L, L, 1}, PmEpi{bias, res, y, act ? 1 : 0}, B, L, s);
+    return df_dispatch<PwGeom>(DfArgs{x, wpk, Ci, Co, 1, L, L, 1}, PwEpi{bias, res, y, act ? 1 : 0}, B, L, s);
 }
 
 extern "C" int lc_pointmlp_groupmax_fwd(const float* x, float* out, int B, int C, int G, int K, int64_t out_bs, int64_t out_cs,

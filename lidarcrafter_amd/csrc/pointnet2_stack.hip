@@ -7,26 +7,20 @@
 //       row the counts do not cover.  No other kernel adds counts up.
 //   pn2_ball_query_kernel   one wave per centre: 64 lanes test 64 consecutive points of the centre's cloud, a ballot and a
 //       prefix popcount keep the hits in ascending index order, the wave stops at nsample hits; the rest of the row is the
-//       first hit, an empty ball is [-1, 0, 0, ...].  d < r2 strictly, d = pn2_dist (the project's expression).
+//       first hit, an empty ball is [-1, 0, 0, ...].  d < r2 strictly, d = lc_dist2 (common.h: the project's expression).
 //   pn2_group_kernel   out[m, c, s] = features[start + idx[m, s], c], zero for an index outside its cloud (forward only).
 //   pn2_three_nn_kernel, pn2_interp_kernel, pn2_interp_bwd_kernel   three nearest known points in ascending (distance,
 //       index) with strict <; out = (w0 f0 + w1 f1) + w2 f2, each operation rounded; the backward pass reads an inverse
 //       table (the stable sort of the indices, built by the caller) and adds every row's terms in ascending (n, j) order.
 //   pn2_voxel_query_kernel   the (dz, dy, dx)-ascending walk over point_indices [B, Z, Y, X], d <= r2.
-//   pn2_sa_first_kernel<CW>   y [Co, M nsample] = relu(W G + bias), G the grouped operand of QueryAndGroup gathered into the
-//       LDS tile of the dense engine (dense_f32.h: its tile, packed weights, chunk of 32 channels, chunk product loop and k
-//       order with the pointwise geometry of pointmlp.hip): the bits of lc_pointmlp_conv_fwd on the materialised tensor.
-#include "dense_f32.h"
+//   Pn2GatherSrc   y [Co, M nsample] = relu(W G + bias), G the grouped operand of QueryAndGroup: the dense engine's kernel
+//       (dense_f32.h df_conv_kernel) with the pointwise geometry and epilogue (dense_pointwise.h), as lc_pointmlp_conv_fwd
+//       runs it, and this operand source in place of the image's: a block resolves its columns to (point row, centre)
+//       pairs in LDS and fills each chunk's tile from the point-major rows.  One kernel body, so the bits are those of
+//       lc_pointmlp_conv_fwd on the materialised tensor.
+#include "dense_pointwise.h"
 
 namespace {
-
-__device__ __forceinline__ float pn2_dist(float x2, float y2, float z2, float x1, float y1, float z1) {
-#pragma clang fp contract(off)
-    const float dx = x2 - x1, dy = y2 - y1, dz = z2 - z1;
-    const float xx = dx * dx, yy = dy * dy, zz = dz * dz;
-    const float s = xx + yy;
-    return s + zz;
-}
 
 // scratch: [0 .. B] offsets of side a, [B + 1 .. 2 B + 1] offsets of side b, then the cloud of every one of the Mb rows
 __global__ __launch_bounds__(256) void pn2_scan_kernel(const int* __restrict__ cnt_a, const int* __restrict__ cnt_b, int B,
@@ -76,7 +70,7 @@ __global__ __launch_bounds__(256) void pn2_ball_query_kernel(const float* __rest
         for (int k0 = 0; k0 < n && cnt < nsample; k0 += 64) {
             const int k = k0 + lane;
             bool hit = false;
-            if (k < n) hit = pn2_dist(cx, cy, cz, p[3 * k], p[3 * k + 1], p[3 * k + 2]) < r2;
+            if (k < n) hit = lc_dist2(cx, cy, cz, p[3 * k], p[3 * k + 1], p[3 * k + 2]) < r2;
             const unsigned long long mask = __ballot(hit);
             if (mask == 0ull) continue;
             if (first < 0) first = k0 + (int)__builtin_ctzll(mask);
@@ -131,7 +125,7 @@ __global__ __launch_bounds__(256) void pn2_three_nn_kernel(const float* __restri
         const float* p = known + (size_t)start * 3;
         const float ux = unknown[3 * (size_t)t], uy = unknown[3 * (size_t)t + 1], uz = unknown[3 * (size_t)t + 2];
         for (int k = 0; k < n; ++k) {
-            const float d = pn2_dist(ux, uy, uz, p[3 * k], p[3 * k + 1], p[3 * k + 2]);
+            const float d = lc_dist2(ux, uy, uz, p[3 * k], p[3 * k + 1], p[3 * k + 2]);
             if (d < b1) {
                 b3 = b2, i3 = i2;
                 b2 = b1, i2 = i1;
@@ -214,7 +208,7 @@ __global__ __launch_bounds__(256) void pn2_voxel_query_kernel(const float* __res
                     if (x < 0 || x >= X) continue;
                     const int k = point_indices[(((size_t)b * Z + z) * Y + y) * X + x];
                     if (k < 0 || k >= N) continue;
-                    const float d = pn2_dist(xyz[3 * (size_t)k], xyz[3 * (size_t)k + 1], xyz[3 * (size_t)k + 2], cx, cy, cz);
+                    const float d = lc_dist2(xyz[3 * (size_t)k], xyz[3 * (size_t)k + 1], xyz[3 * (size_t)k + 2], cx, cy, cz);
                     if (d > r2) continue;
                     if (cnt == 0)
                         for (int l = 0; l < nsample; ++l) row[l] = k;
@@ -230,159 +224,91 @@ __global__ __launch_bounds__(256) void pn2_voxel_query_kernel(const float* __res
 }
 
 // ---- the gathered first layer ----------------------------------------------------------------------------------------
-// the pointwise geometry of csrc/pointmlp.hip (PmGeom): a wave = 32 output channels x 64 columns
-template <int CW_>
-struct Pn2Geom {
-    static constexpr int KC = 32, T = 1, CW = CW_;
-    static constexpr int TH = 1, PXW = 2 * DF_TW;
-    static constexpr bool FLAT = true;
-    static constexpr int S = 1, PADH = 0, PADW = 0;
-    static constexpr int R = 2, NACC = 2;
-    static constexpr int PF_MAX_NLD = 32;
-};
-
-struct Pn2SaArgs {
+// The engine's operand source (dense_f32.h) of the grouped operand [C + xo, L], which is never in memory: column
+// l = m nsample + s is point idx[m, s] of centre m's cloud, rows 0 .. xo - 1 its coordinates minus the centre's, then its
+// features.
+struct Pn2GatherSrc {
     const float* xyz;        // [N, 3]
     const float* new_xyz;    // [M, 3]
     const float* features;   // [N, C] or null (C == 0)
     const int* idx;          // [M, nsample], the ball query's rows: idx[m, 0] < 0 marks an empty ball
     const int* scratch;
-    const float* wpk;
-    const float* bias;
-    float* y;                // [Co, M nsample]
-    int B, C, Co, nsample, use_xyz, vec4;
+    int B, C, nsample, xo, vec4;              // xo: 3 coordinate rows in front of the features, or 0
     long long L;
-};
 
-template <int CW>
-__global__ __launch_bounds__(256, 2) void pn2_sa_first_kernel(Pn2SaArgs a) {
-    using G = Pn2Geom<CW>;
-    using D = DfTile<G>;
-    constexpr int KC = G::KC, CS = D::CS, TWB = D::TWB, NACC = G::NACC;
-    __shared__ float tile[KC * CS];
-    __shared__ int s_row[TWB];                // the column's global point row; -1: it reads none
-    __shared__ int s_ctr[TWB];                // the column's centre; -1: the whole column is zero
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int j = lane & 31, h = lane >> 5;
-    const long long p0 = (long long)blockIdx.x * TWB;
-    const int cb = blockIdx.z * CW + wave % CW;
-    const int pg = wave / CW;
-    const bool live = cb * DF_CO < a.Co;
-    const int xo = a.use_xyz ? 3 : 0, Ci = a.C + xo;
-    const int nchunk = (Ci + KC - 1) / KC;
+    template <class G>
+    struct Stage {
+        static constexpr int KC = G::KC, CS = DfTile<G>::CS, TWB = DfTile<G>::TWB;
+        static constexpr bool LDS_SETUP = true;
+        const Pn2GatherSrc* a;
 
-    for (int c = tid; c < TWB; c += 256) {
-        const long long col = p0 + c;
-        int row = -1, ctr = -1;
-        if (col < a.L) {
-            const int m = (int)(col / a.nsample);
-            const int b = a.scratch[2 * (a.B + 1) + m];
-            if (b >= 0 && a.idx[(size_t)m * a.nsample] >= 0) {
-                const int start = a.scratch[b], n = a.scratch[b + 1] - start;
-                const int i = a.idx[col];
-                ctr = m;
-                if (i >= 0 && i < n) row = start + i;
-            }
+        // per column of the block: [0] its global point row, -1: it reads none; [1] its centre, -1: the whole column is zero
+        __device__ __forceinline__ static int* tables() {
+            __shared__ int t[2][TWB];
+            return t[0];
         }
-        s_row[c] = row;
-        s_ctr[c] = ctr;
-    }
-
-    f32x16 acc[NACC];
-#pragma unroll
-    for (int i = 0; i < NACC; ++i)
-#pragma unroll
-        for (int v = 0; v < 16; ++v) acc[i][v] = 0.f;
-
-    for (int chunk = 0; chunk < nchunk; ++chunk) {
-        __syncthreads();                      // the column tables are written / every wave has read the previous chunk
-        if (chunk == 0 && xo) {
-            for (int t = tid; t < 3 * TWB; t += 256) {
-                const int r = t / TWB, c = t - r * TWB;
-                const int row = s_row[c], ctr = s_ctr[c];
-                float v = 0.f;
-                if (ctr >= 0) v = (row >= 0 ? a.xyz[(size_t)row * 3 + r] : 0.f) - a.new_xyz[(size_t)ctr * 3 + r];
-                tile[r * CS + c] = v;
-            }
-        }
-        // feature quads 4 fq .. 4 fq + 3 that overlap the chunk's channels f_lo .. f_lo + 31 (f = tile channel - xo)
-        const int f_lo = chunk * KC - xo;
-        const int fq0 = f_lo >= 0 ? f_lo / 4 : -1;
-        for (int t = tid; t < 9 * TWB; t += 256) {
-            const int qi = t / TWB, c = t - qi * TWB;
-            const int f0 = 4 * (fq0 + qi);
-            if (f0 + 3 < f_lo || f0 >= f_lo + KC || f0 + 3 < 0) continue;
-            const int row = s_ctr[c] >= 0 ? s_row[c] : -1;
-            float v[4] = {0.f, 0.f, 0.f, 0.f};
-            if (row >= 0) {
-                const float* fp = a.features + (size_t)row * a.C;
-                if (a.vec4 && f0 >= 0 && f0 + 3 < a.C) {
-                    const f32x4 q = *reinterpret_cast<const f32x4*>(fp + f0);
-                    v[0] = q[0], v[1] = q[1], v[2] = q[2], v[3] = q[3];
-                } else {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e)
-                        if (f0 + e >= 0 && f0 + e < a.C) v[e] = fp[f0 + e];
-                }
-            }
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int f = f0 + e, ch = f - f_lo;
-                if (f >= 0 && ch >= 0 && ch < KC) tile[ch * CS + c] = v[e];
-            }
-        }
-        __syncthreads();
-        if (live) {
-            f32x16 part[NACC];
-#pragma unroll
-            for (int i = 0; i < NACC; ++i)
-#pragma unroll
-                for (int v = 0; v < 16; ++v) part[i][v] = 0.f;
-            const f32x4* wp = reinterpret_cast<const f32x4*>(a.wpk) + ((size_t)cb * nchunk + chunk) * ((KC / 8) * 64) + lane;
-            const float* bp = &tile[h * CS + pg * G::PXW + j];
-#pragma unroll
-            for (int q = 0; q < KC / 8; ++q) {
-                const f32x4 w4 = wp[q * 64];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int s = 4 * q + e;
-#pragma unroll
-                    for (int r = 0; r < G::R; ++r) {
-                        const float bv = bp[2 * s * CS + DF_TW * r];
-                        part[r] = __builtin_amdgcn_mfma_f32_32x32x2f32(w4[e], bv, part[r], 0, 0, 0);
+        __device__ __forceinline__ void setup(const Pn2GatherSrc& src, const DfArgs&, int, int p0, int) {
+            a = &src;
+            int* const s_row = tables(), * const s_ctr = s_row + TWB;
+            for (int c = threadIdx.x; c < TWB; c += 256) {
+                const long long col = (long long)p0 + c;
+                int row = -1, ctr = -1;
+                if (col < a->L) {
+                    const int m = (int)(col / a->nsample);
+                    const int b = a->scratch[2 * (a->B + 1) + m];
+                    if (b >= 0 && a->idx[(size_t)m * a->nsample] >= 0) {
+                        const int start = a->scratch[b], n = a->scratch[b + 1] - start;
+                        const int i = a->idx[col];
+                        ctr = m;
+                        if (i >= 0 && i < n) row = start + i;
                     }
                 }
+                s_row[c] = row;
+                s_ctr[c] = ctr;
             }
-#pragma unroll
-            for (int i = 0; i < NACC; ++i) acc[i] += part[i];
         }
-    }
-    if (!live) return;
-
-    const long long px = p0 + pg * G::PXW + j;
+        __device__ __forceinline__ void fill(float* tile, int chunk) const {
+            const int tid = threadIdx.x, xo = a->xo;
+            const int* const s_row = tables(), * const s_ctr = s_row + TWB;
+            if (chunk == 0 && xo) {
+                for (int t = tid; t < 3 * TWB; t += 256) {
+                    const int r = t / TWB, c = t - r * TWB;
+                    const int row = s_row[c], ctr = s_ctr[c];
+                    float v = 0.f;
+                    if (ctr >= 0) v = (row >= 0 ? a->xyz[(size_t)row * 3 + r] : 0.f) - a->new_xyz[(size_t)ctr * 3 + r];
+                    tile[r * CS + c] = v;
+                }
+            }
+            // feature quads 4 fq .. 4 fq + 3 that overlap the chunk's channels f_lo .. f_lo + 31 (f = tile channel - xo)
+            const int f_lo = chunk * KC - xo;
+            const int fq0 = f_lo >= 0 ? f_lo / 4 : -1;
+            for (int t = tid; t < 9 * TWB; t += 256) {
+                const int qi = t / TWB, c = t - qi * TWB;
+                const int f0 = 4 * (fq0 + qi);
+                if (f0 + 3 < f_lo || f0 >= f_lo + KC || f0 + 3 < 0) continue;
+                const int row = s_ctr[c] >= 0 ? s_row[c] : -1;
+                float v[4] = {0.f, 0.f, 0.f, 0.f};
+                if (row >= 0) {
+                    const float* fp = a->features + (size_t)row * a->C;
+                    if (a->vec4 && f0 >= 0 && f0 + 3 < a->C) {
+                        const f32x4 q = *reinterpret_cast<const f32x4*>(fp + f0);
+                        v[0] = q[0], v[1] = q[1], v[2] = q[2], v[3] = q[3];
+                    } else {
 #pragma unroll
-    for (int i = 0; i < NACC; ++i) {
-        const long long ow = px + DF_TW * i;
-        if (ow >= a.L) continue;
+                        for (int e = 0; e < 4; ++e)
+                            if (f0 + e >= 0 && f0 + e < a->C) v[e] = fp[f0 + e];
+                    }
+                }
 #pragma unroll
-        for (int v = 0; v < 16; ++v) {
-            const int co = mfma_row(v, h, cb * DF_CO);
-            if (co >= a.Co) continue;
-            const float val = acc[i][v] + a.bias[co];
-            a.y[(size_t)co * a.L + ow] = val > 0.f ? val : 0.f;
+                for (int e = 0; e < 4; ++e) {
+                    const int f = f0 + e, ch = f - f_lo;
+                    if (f >= 0 && ch >= 0 && ch < KC) tile[ch * CS + c] = v[e];
+                }
+            }
         }
-    }
-}
-
-template <int CW>
-int pn2_sa_first_launch(const Pn2SaArgs& a, lc_stream_t s) {
-    constexpr int TWB = DfTile<Pn2Geom<CW>>::TWB;
-    const long long gx = (a.L + TWB - 1) / TWB, gz = ((a.Co + DF_CO - 1) / DF_CO + CW - 1) / CW;
-    if (gx > 2147483647ll || gz > 65535) return LC_EUNSUP;
-    hipLaunchKernelGGL((pn2_sa_first_kernel<CW>), dim3((unsigned)gx, 1, (unsigned)gz), dim3(256), 0, lc_s(s), a);
-    return lc_launch_status();
-}
+        __device__ __forceinline__ void published(int) {}
+    };
+};
 
 inline unsigned pn2_blocks(long long total) { return (unsigned)((total + 255) / 256); }
 inline bool pn2_grid_ok(long long total) { return (total + 255) / 256 <= 2147483647ll; }
@@ -393,7 +319,7 @@ extern "C" int lc_pn2_limit(int which) {
     switch (which) {
         case 0: return LC_PN2_MAX_NSAMPLE;
         case 1: return LC_PN2_MAX_BATCH;
-        case 2: return DfTile<Pn2Geom<1>>::TWB;
+        case 2: return DfTile<PwGeom<1>>::TWB;
         default: return 0;
     }
 }
@@ -505,9 +431,9 @@ extern "C" int lc_pn2_sa_first_fwd(const float* xyz, const int* xyz_cnt, const f
     if (L > 2147483647ll || N > 715827882) return LC_EUNSUP;
     int e = pn2_scan(xyz_cnt, new_cnt, B, N, M, scratch, s);
     if (e != LC_OK) return e;
-    Pn2SaArgs a{xyz, new_xyz, features, idx, scratch, wpk, bias, y, B, C, Co, nsample, use_xyz ? 1 : 0,
-                (C % 4 == 0 && lc_aligned16(features)) ? 1 : 0, L};
-    if (Co <= 32) return pn2_sa_first_launch<1>(a, s);
-    if (Co <= 64) return pn2_sa_first_launch<2>(a, s);
-    return pn2_sa_first_launch<4>(a, s);
+    const int xo = use_xyz ? 3 : 0, vec4 = (C % 4 == 0 && lc_aligned16(features)) ? 1 : 0;
+    const Pn2GatherSrc src{xyz, new_xyz, features, idx, scratch, B, C, nsample, xo, vec4, L};
+    // the pointwise layer on [1, C + xo, L]: relu, no residual
+    const DfArgs a{nullptr, wpk, C + xo, Co, 1, (int)L, (int)L, 1};
+    return df_dispatch<PwGeom>(a, PwEpi{bias, nullptr, y, 1}, 1, L, s, src);
 }

@@ -44,7 +44,7 @@ struct RnMode {
         static constexpr int lds_off(int r, int t, int ldw) { return (r + dy(t)) * ldw + dx(t); }
         static constexpr int acc_of(int r, int t) { return MODE == 3 ? 2 * r + par(t) : r; }
         static constexpr int out_row(int i) { return MODE == 3 ? i >> 1 : i; }
-        __host__ __device__ static constexpr int out_col(int i, int px) { return MODE == 3 ? 2 * px + (i & 1) : px; }
+        __host__ __device__ static constexpr long long out_col(int i, long long px) { return MODE == 3 ? 2 * px + (i & 1) : px; }
     };
 };
 

@@ -22,7 +22,7 @@ def limit(which: str) -> int:
 
 
 def conv_block_cols(Co: int) -> int:
-    """Columns per block of the pointwise geometry (csrc/pointmlp.hip: PmGeom) for a layer of Co output channels (256 for
+    """Columns per block of the pointwise geometry (csrc/dense_pointwise.h: PwGeom) for a layer of Co output channels (256 for
     Co <= 32, 128 for Co <= 64, else 64)."""
     return limit("tile_l") * (4 if Co <= 32 else (2 if Co <= 64 else 1))
 
