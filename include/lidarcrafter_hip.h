@@ -1323,6 +1323,51 @@ int lc_pn2_sa_first_fwd(const float* xyz, const int* xyz_cnt, const float* new_x
                         const int* idx, const float* wpk, const float* bias, float* y, int* scratch, int B, int N, int M, int C,
                         int Co, int nsample, int use_xyz, lc_stream_t s);
 
+/* ---------------------------------------------------------------------------------------------
+ * Float64 statistics of lidargen/metrics/distribution.py on the device (csrc/stats_f64.hip): the
+ * Frechet distance and the squared MMD.  Contiguous float64 / int32 DEVICE memory unless a stride is given.  Every entry
+ * checks its arguments before any launch (null pointers, sizes < 1: LC_EINVAL; a grid or index range that is not built:
+ * LC_EUNSUP).  No float atomics, every sum in one order that depends on the shapes alone: two calls give the same bits.
+ *   lc_stats_gemm_f64: C [M, N] (row pitch ldc) = sum_k P(i, k) Q(j, k) on v_mfma_f64_16x16x4_f64, P(i, k) =
+ *     P[i p_rs + k p_ks], Q(j, k) = Q[j q_rs + k q_ks] (strides in elements, >= 0), so P Q^T, P^T Q and P Q are one kernel.
+ *     Any M, N, K >= 1; tile edges and K tails are zero-filled in the tile, never read.
+ *   lc_stats_mmd_f64: fx [nx, width], fy [ny, width], table [num_subsets, 2, m] int32: subset s is x = fx[table[s][0]],
+ *     y = fy[table[s][1]] (a row index outside its matrix reads as a zero row).  Per subset and 64 x 64 tile of x x^T, y y^T
+ *     and x y^T the sum of (g / width + 1)^3, the diagonal of the first two dropped, goes to partial
+ *     (lc_stats_mmd_partials(num_subsets, m) doubles); then out [num_subsets, 2] = (the within-set off-diagonal sum, the cross
+ *     sum), the partials added in tile order.  The m x m matrices are never written.
+ *   lc_stats_center_f64: X [n, d], n >= 2 -> mean [d] and A [n, d] = (X - mean) / sqrt(n - 1).
+ *   lc_stats_reduce_f64: *out = the sum over i < n of t(a[i sa], b[i sb]), mode 0: a, 1: a a, 2: (a - b)(a - b),
+ *     3: sqrt(max(a, 0)); scratch: LC_STATS_REDUCE_SCRATCH doubles.
+ *   lc_stats_scale_rows_f64: out [k, k] row i = sqrt(lam[i]) V row i, a zero row where lam[i] <= cut max_j lam[j] (cut >= 0).
+ *   One-sided (Hestenes) Jacobi on the ROWS of W [k, k] (a symmetric matrix is its own transpose), k <= LC_STATS_MAX_EIG:
+ *   lc_stats_jacobi_sweep: one round-robin sweep, k - 1 steps (k for odd k) of floor(k / 2) disjoint row pairs, one launch
+ *     per step.  A pair is rotated when |w_p . w_q| > tol |w_p| |w_q| (never when the norms multiply to zero) and, where
+ *     fro2 is not null, |w_p . w_q| > atol sqrt(*fro2 / k) max(|w_p|, |w_q|) (*fro2: device, the squared Frobenius norm of the
+ *     matrix; the left side over the larger norm is the entry (p, q) of V S V^T); V (may be null; lc_stats_jacobi_init
+ *     writes the identity) receives the same rotations.  *flag (device int32): 1 if any pair was
+ *     rotated in this sweep, else 0.  At convergence row i of W is lambda_i times eigenvector i and row i of V eigenvector i.
+ *   lc_stats_jacobi_values: lam [k] = the row norms of W (the absolute eigenvalues).
+ *   lc_stats_jacobi_pair (host only): pq[0] < pq[1] the pair of (step, slot) for this k >= 2, pq[1] = -1 for the idle slot.
+ *   lc_stats_limit(i): 0 LC_STATS_MAX_EIG, 1 LC_STATS_REDUCE_SCRATCH. */
+#define LC_STATS_MAX_EIG 4096
+#define LC_STATS_REDUCE_SCRATCH 1024
+int lc_stats_limit(int which);
+int lc_stats_jacobi_pair(int k, int step, int slot, int* pq);
+int lc_stats_gemm_f64(const double* P, int64_t p_rs, int64_t p_ks, const double* Q, int64_t q_rs, int64_t q_ks, double* C,
+                      int64_t ldc, int M, int N, int K, lc_stream_t s);
+int64_t lc_stats_mmd_partials(int num_subsets, int m);
+int lc_stats_mmd_f64(const double* fx, int nx, const double* fy, int ny, int width, const int32_t* table, int num_subsets,
+                     int m, double* partial, double* out, lc_stream_t s);
+int lc_stats_center_f64(const double* X, int n, int d, double* mean, double* A, lc_stream_t s);
+int lc_stats_reduce_f64(const double* a, int64_t sa, const double* b, int64_t sb, int64_t n, int mode, double* scratch,
+                        double* out, lc_stream_t s);
+int lc_stats_scale_rows_f64(const double* V, const double* lam, int k, double cut, double* out, lc_stream_t s);
+int lc_stats_jacobi_init(double* V, int k, lc_stream_t s);
+int lc_stats_jacobi_sweep(double* W, double* V, int k, double tol, double atol, const double* fro2, int32_t* flag,
+                          lc_stream_t s);
+int lc_stats_jacobi_values(const double* W, int k, double* lam, lc_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

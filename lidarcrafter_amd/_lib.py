@@ -253,6 +253,17 @@ SIGNATURES = {
     "lc_pn2_three_interpolate_bwd": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, vp]),
     "lc_pn2_voxel_query_fwd": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, i32, i32, i32, vp]),
     "lc_pn2_sa_first_fwd": (i32, [vp] * 10 + [i32] * 7 + [vp]),
+    "lc_stats_limit": (i32, [i32]),
+    "lc_stats_jacobi_pair": (i32, [i32, i32, i32, C.POINTER(C.c_int)]),
+    "lc_stats_gemm_f64": (i32, [vp, i64, i64, vp, i64, i64, vp, i64, i32, i32, i32, vp]),
+    "lc_stats_mmd_partials": (i64, [i32, i32]),
+    "lc_stats_mmd_f64": (i32, [vp, i32, vp, i32, i32, vp, i32, i32, vp, vp, vp]),
+    "lc_stats_center_f64": (i32, [vp, i32, i32, vp, vp, vp]),
+    "lc_stats_reduce_f64": (i32, [vp, i64, vp, i64, i64, i32, vp, vp, vp]),
+    "lc_stats_scale_rows_f64": (i32, [vp, vp, i32, f64, vp, vp]),
+    "lc_stats_jacobi_init": (i32, [vp, i32, vp]),
+    "lc_stats_jacobi_sweep": (i32, [vp, vp, i32, f64, f64, vp, vp, vp]),
+    "lc_stats_jacobi_values": (i32, [vp, i32, vp, vp]),
 }
 
 _lib = None

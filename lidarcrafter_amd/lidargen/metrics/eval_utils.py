@@ -119,59 +119,68 @@ def extract_point_features(model, clouds, batch_size=16, scale=1 / 80.0):
     return np.stack(rows) if rows else np.zeros((0, 0))
 
 
+def _stats(stats_device, key="device"):
+    """Keyword for the functions of `distribution` (or, as `stats_device`, for compute_fd): nothing for the host route (the
+    default, so those calls stay as they were), the device for the float64 kernels (distribution's docstring)."""
+    return {} if stats_device is None else {key: stats_device}
+
+
 def _as_features(a, model, batch_size):
     if isinstance(a, np.ndarray) and a.ndim == 2 and a.shape[1] != 3:
         return a                                    # already a feature matrix (the evaluator caches the real set's)
     return extract_point_features(model, a, batch_size)
 
 
-def compute_fpd(reference, samples, model, batch_size=16, columns=None):
+def compute_fpd(reference, samples, model, batch_size=16, columns=None, stats_device=None):
     """Score of Frechet Point Distance (FPD): the Frechet distance of the PointNet features of the two sets.  Either set
     may be a feature matrix ([n, width] numpy array) instead of a list of clouds.  `columns` (a slice or index array)
-    restricts the distance to those feature columns."""
+    restricts the distance to those feature columns.  `stats_device`: None the host statistics, 'cuda' the device route."""
     print("Evaluating (FPD) ...")
     fr, fs = _as_features(reference, model, batch_size), _as_features(samples, model, batch_size)
     if columns is not None:
         fr, fs = fr[:, columns], fs[:, columns]
-    score = distribution.compute_frechet_distance(fr, fs)
+    score = distribution.compute_frechet_distance(fr, fs, **_stats(stats_device))
     print(OUTPUT_TEMPLATE.format("FPD ", score))
     return score
 
 
-def compute_fd(reference, samples):
-    """Frechet distance of two feature matrices as the reference's evaluator computes it (eval_utils.py:98-102)."""
+def compute_fd(reference, samples, stats_device=None):
+    """Frechet distance of two feature matrices as the reference's evaluator computes it (eval_utils.py:98-102).
+    `stats_device`: None the host statistics; 'cuda' the device route on the feature matrices themselves."""
+    if stats_device is not None:
+        return distribution.compute_frechet_distance(reference, samples, device=stats_device)
     mu1, mu2 = np.mean(reference, axis=0), np.mean(samples, axis=0)
     sigma1, sigma2 = np.cov(reference, rowvar=False), np.cov(samples, rowvar=False)
     return distribution.calculate_frechet_distance(mu1, sigma1, mu2, sigma2)
 
 
-def compute_fsvd(reference, samples, data, model=None):
+def compute_fsvd(reference, samples, data, model=None, stats_device=None):
     """Score of Frechet Sparse Volume Distance (FSVD): the Frechet distance of the depth-sector means of the MinkUNet
     features of the two sets of [N, 3] clouds.  `model`: the extractor to use instead of the pretrained one."""
     print("Evaluating (FSVD) ...")
     gt_logits, samples_logits = metric_utils.compute_logits(data, "voxel", reference, samples, model=model)
-    score = compute_fd(gt_logits, samples_logits)
+    score = compute_fd(gt_logits, samples_logits, **_stats(stats_device, "stats_device"))
     print(OUTPUT_TEMPLATE.format("FSVD", score))
     return score
 
 
-def compute_fpvd(reference, samples, data, model=None):
+def compute_fpvd(reference, samples, data, model=None, stats_device=None):
     """Score of Frechet Point-Voxel Distance (FPVD): the Frechet distance of the depth-sector means of the SPVCNN
     features of the two sets of [N, 3] clouds.  `model`: the extractor to use instead of the pretrained one."""
     print("Evaluating (FPVD) ...")
     gt_logits, samples_logits = metric_utils.compute_point_voxel_logits(data, reference, samples, model=model)
-    score = compute_fd(gt_logits, samples_logits)
+    score = compute_fd(gt_logits, samples_logits, **_stats(stats_device, "stats_device"))
     print(OUTPUT_TEMPLATE.format("FPVD", score))
     return score
 
 
-def compute_frid(reference, samples, data, model=None, size=None):
+def compute_frid(reference, samples, data, model=None, size=None, stats_device=None):
     """Score of Frechet Range Image Distance (FRID): the Frechet distance of the row-band means of RangeNet's decoder map
     over the range images of the two sets of [N, 3] clouds.  `model`: the extractor to use instead of the pretrained one;
     `size`: (H, W) of the range images instead of the dataset's."""
     print("Evaluating (FRID) ...")
     gt_logits, samples_logits = metric_utils.compute_range_logits(data, reference, samples, model=model, size=size)
-    score = compute_fd(gt_logits, samples_logits)
+    score = compute_fd(gt_logits, samples_logits, **_stats(stats_device, "stats_device"))
     print(OUTPUT_TEMPLATE.format("FRID", score))
     return score
 
@@ -198,7 +207,7 @@ def extract_range_features(model, preprocess, imgs, masks=None, batch_size=16):
     return np.concatenate(rows) if rows else np.zeros((0, 0))
 
 
-def compute_frd(reference, samples, model, preprocess=None, batch_size=16, columns=None):
+def compute_frd(reference, samples, model, preprocess=None, batch_size=16, columns=None, stats_device=None):
     """Score of Frechet Range Distance (FRD) of the reference's own evaluator: the Frechet distance of the RangeNet
     'lidargen' features of the two sets of range images.  Either set may be a feature matrix ([n, width] numpy array)
     instead of [n, C, H, W] images.  `columns` (a slice or index array) restricts the distance to those feature columns."""
@@ -208,22 +217,23 @@ def compute_frd(reference, samples, model, preprocess=None, batch_size=16, colum
              for a in (reference, samples)]
     if columns is not None:
         feats = [f[:, columns] for f in feats]
-    score = distribution.compute_frechet_distance(feats[0], feats[1])
+    score = distribution.compute_frechet_distance(feats[0], feats[1], **_stats(stats_device))
     print(OUTPUT_TEMPLATE.format("FRD ", score))
     return score
 
 
-def compute_obj_scores(real_set, gen_set, class_name="car"):
+def compute_obj_scores(real_set, gen_set, class_name="car", stats_device=None):
     """The evaluator's 'obj' block (tools/evaluation/evaluate_our.py:424-439) on two object sets of
     `fg_object.get_fg_object_set_feature`: {'frechet_distance', 'squared_mmd'} of the PointMLP features and {'jsd', 'mmd'} of
-    the object BEV histograms of `class_name`.  One score line per number."""
+    the object BEV histograms of `class_name`.  One score line per number.  `stats_device`: None the host statistics, 'cuda'
+    the device route for the first two."""
     from . import bev
 
     real, gen = real_set[class_name], gen_set[class_name]
     dev = "cuda" if torch.cuda.is_available() else "cpu"
     hists = [torch.from_numpy(np.asarray(s["bev_hists"])).to(dev).float() for s in (real, gen)]
-    out = {"frechet_distance": float(distribution.compute_frechet_distance(real["pts_feat"], gen["pts_feat"])),
-           "squared_mmd": float(distribution.compute_squared_mmd(real["pts_feat"], gen["pts_feat"])),
+    out = {"frechet_distance": float(distribution.compute_frechet_distance(real["pts_feat"], gen["pts_feat"], **_stats(stats_device))),
+           "squared_mmd": float(distribution.compute_squared_mmd(real["pts_feat"], gen["pts_feat"], **_stats(stats_device))),
            "jsd": float(bev.compute_jsd_2d(*hists)),
            "mmd": float(bev.compute_mmd_2d(*hists))}
     for name, key in (("OFD ", "frechet_distance"), ("OMMD", "squared_mmd"), ("OJSD", "jsd"), ("OBMD", "mmd")):
