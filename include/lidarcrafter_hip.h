@@ -1368,6 +1368,31 @@ int lc_stats_jacobi_sweep(double* W, double* V, int k, double tol, double atol, 
                           lc_stream_t s);
 int lc_stats_jacobi_values(const double* W, int k, double* lam, lc_stream_t s);
 
+/* ---------------------------------------------------------------------------------------------
+ * The step in front of the FRID / FSVD / FPVD networks on the device, a ragged batch of clouds at a time
+ * (csrc/metric_preprocess.hip; lidargen/metrics/metric_utils.py preprocess_range, preprocess_pcd +
+ * pcd2voxel + sparse_collate).  pts: contiguous [N, 3] float32 (is_f64 = 0) or float64 (1); offsets: int32 [B + 1],
+ * offsets[0] = 0, non-decreasing, offsets[B] = N (the CALLER guarantees it; a kernel only ever derives a cloud index in
+ * [0, B) from them).  0 <= lo < hi: the open depth interval.  Integer atomics only: two calls give the same bits.
+ *   lc_range_batch_fwd: out float32 [B, 4, H, W] = (depth, x, y, z) of preprocess_range applied to each cloud WIDENED TO
+ *     FLOAT64.  zbuf: uint32 [B, H, W] scratch.  dir: float64 [3, H, W], the ray directions of range2xyz at the pixel
+ *     centres.  fov_down_abs, fov_range: |fov_down| and |fov_down| + |fov_up| in radians.  lo32, hi32: the bounds rounded to
+ *     float32 (range2xyz's mask on the float32 depth image).  N = 0 is legal (every pixel -1).
+ *   lc_voxel_batch_fwd: feats float32 [n, 4] = (the first point of each voxel, -1), coords int32 [n, 4] = (rint(p / voxel)
+ *     - the cloud's minimum, cloud index), out_offsets int32 [B + 1]; n = out_offsets[B] <= N rows are written, feats and
+ *     coords hold N rows.  Filter and quotient in the dtype of pts (lo, hi, voxel rounded to it).  N >= 1.
+ *     scratch: lc_voxel_batch_scratch_bytes(N, B) bytes.
+ *   lc_voxel_batch_key_bits (host only): bits[0] = the bits of the cloud field of the sort key (values 0 ... B), bits[1] =
+ *     those of the three axis fields (each holds q + R, R = ceil(hi / voxel) + 2); LC_EUNSUP when they exceed 64 together,
+ *     which lc_voxel_batch_fwd refuses alike. */
+int lc_range_batch_fwd(const void* pts, int is_f64, const int32_t* offsets, int B, int N, int H, int W, double lo, double hi,
+                       float lo32, float hi32, double fov_down_abs, double fov_range, const double* dir, uint32_t* zbuf,
+                       float* out, lc_stream_t s);
+int lc_voxel_batch_key_bits(int B, double hi, double voxel, int32_t* bits);
+int64_t lc_voxel_batch_scratch_bytes(int N, int B);
+int lc_voxel_batch_fwd(const void* pts, int is_f64, const int32_t* offsets, int B, int N, double lo, double hi, double voxel,
+                       void* scratch, float* feats, int32_t* coords, int32_t* out_offsets, lc_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -264,6 +264,10 @@ SIGNATURES = {
     "lc_stats_jacobi_init": (i32, [vp, i32, vp]),
     "lc_stats_jacobi_sweep": (i32, [vp, vp, i32, f64, f64, vp, vp, vp]),
     "lc_stats_jacobi_values": (i32, [vp, i32, vp, vp]),
+    "lc_range_batch_fwd": (i32, [vp, i32, vp, i32, i32, i32, i32, f64, f64, f32, f32, f64, f64, vp, vp, vp, vp]),
+    "lc_voxel_batch_key_bits": (i32, [i32, f64, f64, C.POINTER(C.c_int32)]),
+    "lc_voxel_batch_scratch_bytes": (i64, [i32, i32]),
+    "lc_voxel_batch_fwd": (i32, [vp, i32, vp, i32, i32, f64, f64, f64, vp, vp, vp, vp, vp]),
 }
 
 _lib = None

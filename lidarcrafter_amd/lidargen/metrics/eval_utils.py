@@ -154,32 +154,39 @@ def compute_fd(reference, samples, stats_device=None):
     return distribution.calculate_frechet_distance(mu1, sigma1, mu2, sigma2)
 
 
-def compute_fsvd(reference, samples, data, model=None, stats_device=None):
+def compute_fsvd(reference, samples, data, model=None, stats_device=None, preprocess_device=None):
     """Score of Frechet Sparse Volume Distance (FSVD): the Frechet distance of the depth-sector means of the MinkUNet
-    features of the two sets of [N, 3] clouds.  `model`: the extractor to use instead of the pretrained one."""
+    features of the two sets of [N, 3] clouds.  `model`: the extractor to use instead of the pretrained one.
+    `preprocess_device`: None quantizes the clouds on the host, 'cuda' a batch at a time on the device (the same bits)."""
     print("Evaluating (FSVD) ...")
-    gt_logits, samples_logits = metric_utils.compute_logits(data, "voxel", reference, samples, model=model)
+    gt_logits, samples_logits = metric_utils.compute_logits(data, "voxel", reference, samples, model=model,
+                                                            preprocess_device=preprocess_device)
     score = compute_fd(gt_logits, samples_logits, **_stats(stats_device, "stats_device"))
     print(OUTPUT_TEMPLATE.format("FSVD", score))
     return score
 
 
-def compute_fpvd(reference, samples, data, model=None, stats_device=None):
+def compute_fpvd(reference, samples, data, model=None, stats_device=None, preprocess_device=None):
     """Score of Frechet Point-Voxel Distance (FPVD): the Frechet distance of the depth-sector means of the SPVCNN
-    features of the two sets of [N, 3] clouds.  `model`: the extractor to use instead of the pretrained one."""
+    features of the two sets of [N, 3] clouds.  `model`: the extractor to use instead of the pretrained one.
+    `preprocess_device`: as for `compute_fsvd`."""
     print("Evaluating (FPVD) ...")
-    gt_logits, samples_logits = metric_utils.compute_point_voxel_logits(data, reference, samples, model=model)
+    gt_logits, samples_logits = metric_utils.compute_point_voxel_logits(data, reference, samples, model=model,
+                                                                        preprocess_device=preprocess_device)
     score = compute_fd(gt_logits, samples_logits, **_stats(stats_device, "stats_device"))
     print(OUTPUT_TEMPLATE.format("FPVD", score))
     return score
 
 
-def compute_frid(reference, samples, data, model=None, size=None, stats_device=None):
+def compute_frid(reference, samples, data, model=None, size=None, stats_device=None, preprocess_device=None):
     """Score of Frechet Range Image Distance (FRID): the Frechet distance of the row-band means of RangeNet's decoder map
     over the range images of the two sets of [N, 3] clouds.  `model`: the extractor to use instead of the pretrained one;
-    `size`: (H, W) of the range images instead of the dataset's."""
+    `size`: (H, W) of the range images instead of the dataset's.  `preprocess_device`: None projects the clouds on the host,
+    'cuda' a batch at a time on the device -- the host's bits for float64 clouds, the host route of the cloud widened to
+    float64 for float32 ones (metric_utils.preprocess_range_batch)."""
     print("Evaluating (FRID) ...")
-    gt_logits, samples_logits = metric_utils.compute_range_logits(data, reference, samples, model=model, size=size)
+    gt_logits, samples_logits = metric_utils.compute_range_logits(data, reference, samples, model=model, size=size,
+                                                                  preprocess_device=preprocess_device)
     score = compute_fd(gt_logits, samples_logits, **_stats(stats_device, "stats_device"))
     print(OUTPUT_TEMPLATE.format("FRID", score))
     return score

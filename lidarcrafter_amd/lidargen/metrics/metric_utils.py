@@ -10,7 +10,10 @@ aggregation of `batch2list` :351-365 on the device) and the point-voxel one (`co
 input and aggregation around the SPVCNN) and the range-image one (`pcd2range` :69-122, `range2xyz` :125-154,
 `preprocess_range` :317-322 in numpy on the host, `compute_range_logits`: RangeNet over 5-channel range images, row-band
 means on the device).  `compute_logits` still refuses 'point_voxel' and 'range' by name (its callers rely on that) and
-points at `compute_point_voxel_logits` / `compute_range_logits`."""
+points at `compute_point_voxel_logits` / `compute_range_logits`.
+With `preprocess_device='cuda'` the three front-ends prepare a whole batch of clouds on the device instead of cloud by cloud
+on the host (`preprocess_range_batch`, `pcd2voxel_batch`; csrc/metric_preprocess.hip); None, the
+default, is the host route, unchanged."""
 from __future__ import annotations
 
 import math
@@ -19,6 +22,7 @@ import numpy as np
 import torch
 
 from lidarcrafter_amd import ops as K
+from lidarcrafter_amd import ops_metric_pre as KP
 from lidarcrafter_amd import ops_spconv as KS
 
 # lidargen/metrics/__init__.py:28-33
@@ -176,6 +180,33 @@ def sparse_collate(batch, device=None):
     return feats, coords, torch.cumsum(counts, 0).to(torch.int32).to(device)
 
 
+def pcd2voxel_batch(clouds, device="cuda", depth_range=None, **kwargs):
+    """A list of [N, 3] clouds -> the triple `sparse_collate([pcd2voxel(preprocess_pcd(c, depth_range=...)) for c in
+    clouds], device)` returns, bit for bit, computed on the device in one pass over the batch: one upload (numpy clouds; CUDA
+    tensors are concatenated on the device), one sort, one device->host read (lc_voxel_batch_fwd).  Depth filter and
+    rint(p / 0.05) run in the clouds' own dtype, float32 or float64, as numpy runs them; the quotient is the IEEE division.
+    (The per-cloud route of a CUDA tensor through `pcd2voxel` divides as torch does, by multiplying with 1 / 0.05 = 20: the
+    two agree wherever p * 20 is exact.)  There is no fallback: without a GPU, or for a `device` that is not a CUDA(HIP)
+    device, it raises; an empty list raises as `sparse_collate` does.  Further keywords are ignored, as by `preprocess_pcd`:
+    a whole DATASET_CONFIG entry may be passed."""
+    if depth_range is None:
+        raise TypeError("pcd2voxel_batch: `depth_range` is required (DATASET_CONFIG[...]['depth_range'])")
+    clouds = list(clouds)
+    if not clouds:
+        raise ValueError("pcd2voxel_batch: an empty batch")
+    KP.voxel_key_bits(len(clouds), float(depth_range[1]), VOXEL_SIZE)
+    pts, offsets = KP.ragged(clouds, device)
+    return KP.voxelize(pts, offsets, depth_range, VOXEL_SIZE)
+
+
+def check_preprocess_device(preprocess_device, need_gpu=True):
+    """None: the host route.  Otherwise the CUDA(HIP) device of the batched route; anything else raises ValueError, a
+    missing GPU RuntimeError (`need_gpu=False` checks the value alone)."""
+    if preprocess_device is None:
+        return None
+    return KP._device(preprocess_device, need_gpu)
+
+
 def sector_edges(depth_range):
     """The 17 float32 edges of the 16 depth sectors (batch2list 'depth', metric_utils.py:357-358)."""
     from . import NUM_SECTORS
@@ -185,33 +216,39 @@ def sector_edges(depth_range):
     return e
 
 
-def _sector_features(data_type, modality, model, sets):
+def _sector_features(data_type, modality, model, sets, preprocess_device=None):
     """Per list of [N, 3] clouds in `sets` the float32 [n, 16 * width] depth-sector means of `model`'s features,
-    MODAL2BATCHSIZE[modality] clouds at a time."""
+    MODAL2BATCHSIZE[modality] clouds at a time.  `preprocess_device`: None quantizes cloud by cloud (`pcd2voxel`), 'cuda' a
+    batch at a time on the device (`pcd2voxel_batch`)."""
     from . import DATASET_CONFIG, MODAL2BATCHSIZE, TYPE2DATASET
 
     cfg = DATASET_CONFIG[TYPE2DATASET[data_type]]
     bs = MODAL2BATCHSIZE[modality]
     dev = next(model.parameters()).device
     edges = sector_edges(cfg["depth_range"]).to(dev)
+    pre = check_preprocess_device(preprocess_device)
     output = tuple()
     for data in sets:
         rows = []
         for i in range(math.ceil(len(data) / bs)):
-            batch = [pcd2voxel(preprocess_pcd(pcd, **cfg)) for pcd in data[i * bs:(i + 1) * bs]]
-            feats, coords, offsets = sparse_collate(batch, dev)
+            if pre is None:
+                batch = [pcd2voxel(preprocess_pcd(pcd, **cfg)) for pcd in data[i * bs:(i + 1) * bs]]
+                feats, coords, offsets = sparse_collate(batch, dev)
+            else:
+                feats, coords, offsets = pcd2voxel_batch(data[i * bs:(i + 1) * bs], dev, depth_range=cfg["depth_range"])
             out = model(feats, coords, return_final_logits=True)
             rows.append(KS.sector_means(out["logits"], coords, offsets, edges, VOXEL_SIZE).cpu().numpy())
         output += (np.concatenate(rows) if rows else np.zeros((0, 0), np.float32),)
     return output
 
 
-def compute_logits(data_type, modality, *args, model=None, root=None):
+def compute_logits(data_type, modality, *args, model=None, root=None, preprocess_device=None):
     """For every list of [N, 3] clouds in `args` the float32 [n, 16 * width] matrix of depth-sector means of the
     extractor's features (metric_utils.py:374-412), MODAL2BATCHSIZE clouds at a time.  Only 'voxel' (MinkowskiNet, FSVD)
     is dispatched from here; 'point_voxel' (SPVCNN, FPVD) is `compute_point_voxel_logits`, 'range' (RangeNet, FRID) is
     `compute_range_logits`.  `model`: a minkowskinet Model
-    in eval mode on the GPU; None builds the pretrained one (build_model)."""
+    in eval mode on the GPU; None builds the pretrained one (build_model).  `preprocess_device`: None quantizes on the host,
+    'cuda' on the device a batch at a time (`pcd2voxel_batch`: the same bits)."""
     from . import MODALITY2MODEL, TYPE2DATASET, build_model
 
     assert data_type in ["32", "64"]
@@ -222,28 +259,30 @@ def compute_logits(data_type, modality, *args, model=None, root=None):
     if modality != "voxel":
         raise NotImplementedError(f"compute_logits: modality '{modality}' ({MODALITY2MODEL[modality]}) is not dispatched "
                                   "from here; call metric_utils.compute_range_logits(data_type, *sets)")
+    check_preprocess_device(preprocess_device, need_gpu=False)
     if not torch.cuda.is_available():
         raise RuntimeError("compute_logits needs the MI355X: no CPU fallback on the hot path")
     if model is None:
         model = build_model(TYPE2DATASET[data_type], MODALITY2MODEL[modality], device="cuda", root=root)
-    return _sector_features(data_type, modality, model, args)
+    return _sector_features(data_type, modality, model, args, preprocess_device)
 
 
-def compute_point_voxel_logits(data_type, *sets, model=None, root=None):
+def compute_point_voxel_logits(data_type, *sets, model=None, root=None, preprocess_device=None):
     """For every list of [N, 3] clouds in `sets` the float32 [n, 16 * 48 = 768] matrix of depth-sector means of the
     SPVCNN's per-point features (the reference's compute_logits for 'point_voxel'), 25 clouds at a time.  The points are
     the unique voxels of pcd2voxel; their sector is decided from the integer voxel coordinate (the
     reference feeds the float coordinate, which is that integer or 1 ulp above it).  `model`: a spvcnn Model in eval mode
-    on the GPU; None loads the pretrained one (models.spvcnn.pretrained)."""
+    on the GPU; None loads the pretrained one (models.spvcnn.pretrained).  `preprocess_device`: as in `compute_logits`."""
     from . import TYPE2DATASET
     from .models import spvcnn
 
     assert data_type in ["32", "64"]
+    check_preprocess_device(preprocess_device, need_gpu=False)
     if not torch.cuda.is_available():
         raise RuntimeError("compute_point_voxel_logits needs the MI355X: no CPU fallback on the hot path")
     if model is None:
         model = spvcnn.pretrained(TYPE2DATASET[data_type], device="cuda", root=root)
-    return _sector_features(data_type, "point_voxel", model, sets)
+    return _sector_features(data_type, "point_voxel", model, sets, preprocess_device)
 
 
 # ---- the range-image front-end (FRID) -----------------------------------------------------------------------------
@@ -306,14 +345,41 @@ def preprocess_range(pcd, **kwargs):
     return np.vstack([depth_img[None], xyz_img])
 
 
-def compute_range_logits(data_type, *sets, model=None, root=None, size=None):
+def preprocess_range_batch(clouds, device="cuda", remission=None, labels=None, **cfg):
+    """A list of [N, 3] clouds -> float32 [B, 4, H, W] on the device: depth on top of its back-projection, computed by
+    lc_range_batch_fwd in one pass over the batch (`cfg`: size, fov, depth_range as for `preprocess_range`).
+    The contract: the result is `torch.from_numpy(np.stack([preprocess_range(c.astype(np.float64), **cfg) for c in
+    clouds])).float()` -- the host route applied to the clouds WIDENED TO FLOAT64.  For float64 clouds that is the host route
+    itself; for float32 clouds numpy evaluates norm / arctan2 / arcsin in float32, which no device routine reproduces bit for
+    bit: a few points per 100 000 fall into a neighbouring pixel and about one depth in ten differs by one float32 ulp
+    (DESIGN.md section 5u has the figures).  The pixel of a point
+    whose float64 coordinate lies within about 1e-12 px of a pixel boundary depends on the library's atan2 / asin.
+    `remission=` / `labels=` images depend on the order of equal depths on the host and are refused.  No fallback: without
+    a GPU, or for a `device` that is not a CUDA(HIP) device, it raises; an empty list raises."""
+    if remission is not None:
+        raise NotImplementedError("preprocess_range_batch: `remission=` is not built on the device route (the host writes "
+                                  "the feature of the last of equally deep points); use preprocess_range / pcd2range")
+    if labels is not None:
+        raise NotImplementedError("preprocess_range_batch: `labels=` is not built on the device route (the host writes the "
+                                  "label of the last of equally deep points); use preprocess_range / pcd2range")
+    clouds = list(clouds)
+    if not clouds:
+        raise ValueError("preprocess_range_batch: an empty batch")
+    pts, offsets = KP.ragged([np.asarray(c) if not isinstance(c, torch.Tensor) else c for c in clouds], device)
+    return KP.range_images(pts, offsets, cfg["size"], cfg["fov"], cfg["depth_range"])
+
+
+def compute_range_logits(data_type, *sets, model=None, root=None, size=None, preprocess_device=None):
     """For every list of [N, 3] clouds in `sets` the float32 [n, 16 * 32 = 512] matrix of row-band means of RangeNet's
     decoder map over the clouds' range images (the reference's compute_logits for 'range'), MODAL2BATCHSIZE['range']
     clouds at a time.  The projection runs in numpy on the host.  `model`: a models.rangenet Model in eval mode on the
-    GPU; None loads the pretrained one (build_model).  `size`: (H, W) instead of the dataset's image size."""
+    GPU; None loads the pretrained one (build_model).  `size`: (H, W) instead of the dataset's image size.
+    `preprocess_device`: None projects on the host, 'cuda' on the device a batch at a time (`preprocess_range_batch`: the
+    host route's bits for float64 clouds, the host route of the widened cloud for float32 ones)."""
     from . import AGG_TYPE, DATASET_CONFIG, MODAL2BATCHSIZE, TYPE2DATASET, build_model
 
     assert data_type in ["32", "64"]
+    check_preprocess_device(preprocess_device, need_gpu=False)
     if not torch.cuda.is_available():
         raise RuntimeError("compute_range_logits needs the MI355X: no CPU fallback on the hot path")
     cfg = dict(DATASET_CONFIG[TYPE2DATASET[data_type]])
@@ -323,12 +389,17 @@ def compute_range_logits(data_type, *sets, model=None, root=None, size=None):
         model = build_model(TYPE2DATASET[data_type], "rangenet", device="cuda", root=root)
     bs = MODAL2BATCHSIZE["range"]
     dev = next(model.parameters()).device
+    pre = check_preprocess_device(preprocess_device)
     output = tuple()
     for data in sets:
         rows = []
         for i in range(math.ceil(len(data) / bs)):
-            batch = np.stack([preprocess_range(np.asarray(pcd), **cfg) for pcd in data[i * bs:(i + 1) * bs]])
+            if pre is None:
+                batch = np.stack([preprocess_range(np.asarray(pcd), **cfg) for pcd in data[i * bs:(i + 1) * bs]])
+                x = torch.from_numpy(batch).float().to(dev)
+            else:
+                x = preprocess_range_batch(data[i * bs:(i + 1) * bs], dev, **cfg)
             with torch.no_grad():
-                rows.append(model(torch.from_numpy(batch).float().to(dev), return_final_logits=True, agg_type=AGG_TYPE))
+                rows.append(model(x, return_final_logits=True, agg_type=AGG_TYPE))
         output += (np.vstack(rows) if rows else np.zeros((0, 0), np.float32),)
     return output
