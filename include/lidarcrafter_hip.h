@@ -930,6 +930,22 @@ int lc_chamfer3d_fwd(const float* xyz1, const float* xyz2, int B, int N, int M, 
  * d = dx*dx + dy*dy with separate float32 roundings, first minimum wins.  B <= 65535 (LC_EUNSUP otherwise). */
 int lc_chamfer2d_fwd(const float* xyz1, const float* xyz2, int B, int N, int M, float* dist1,
                      int32_t* idx1, float* dist2, int32_t* idx2, lc_stream_t s);
+/* Chamfer distance backward (chamfer3D.cu:155-195 NmDistanceGradKernel, chamfer2D.cu:145-171; csrc/chamfer_bwd.hip,
+ * DESIGN.md section 5v): xyz1 [B,N,D], xyz2 [B,M,D], grad_dist1 [B,N], grad_dist2 [B,M], idx1 [B,N], idx2 [B,M] as the
+ * forward writes them -> grad_xyz1 [B,N,D], grad_xyz2 [B,M,D], D = 3 / 2.  Terms g = grad * 2, t = g * (own - other), each
+ * operation rounded to float32; no float atomics: row j of grad_xyz1 = (+0 + its direct term) + the terms
+ * -(2 grad_dist2[k] (xyz2[k] - xyz1[j])) of the k with idx2[k] == j in ascending k (more than 32 of them: 256 strided lane
+ * sums and a halving tree, csrc/chamfer_bwd.hip); grad_xyz2 likewise.  An index outside its cloud adds no term.  The table
+ * of the k of every j is built on the device in `scratch` (lc_chamfer_bwd_scratch_bytes(B, N, M) bytes, 0 for sizes the
+ * entries refuse): one stable radix sort of the B (N + M) indices and a binary search per row, no host read.
+ * Any B (also for D = 2); B (N + M) < 2^31 - 1 (LC_EUNSUP otherwise). */
+int64_t lc_chamfer_bwd_scratch_bytes(int B, int N, int M);
+int lc_chamfer3d_bwd(const float* xyz1, const float* xyz2, const float* grad_dist1, const float* grad_dist2,
+                     const int32_t* idx1, const int32_t* idx2, int B, int N, int M, float* grad_xyz1, float* grad_xyz2,
+                     void* scratch, lc_stream_t s);
+int lc_chamfer2d_bwd(const float* xyz1, const float* xyz2, const float* grad_dist1, const float* grad_dist2,
+                     const int32_t* idx1, const int32_t* idx2, int B, int N, int M, float* grad_xyz1, float* grad_xyz2,
+                     void* scratch, lc_stream_t s);
 /* Chamfer distance of BEV cell sets on their nx x ny grid (csrc/bev_chamfer.hip).
  * lc_bev_grid_supported: LC_OK when the distance transform takes the grid; LC_EINVAL for a non-positive size; LC_EUNSUP
  *   when 2 nx^2 ny^2 >= 2^32 (the u32 distances would overflow) or a 64-column strip of it does not fit 64 KiB of LDS.

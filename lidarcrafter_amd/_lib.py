@@ -186,6 +186,9 @@ SIGNATURES = {
     "lc_rbf_kernel_sum": (i32, [vp, vp, i32, i32, i32, f32, vp, vp]),
     "lc_chamfer3d_fwd": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]),
     "lc_chamfer2d_fwd": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]),
+    "lc_chamfer_bwd_scratch_bytes": (i64, [i32, i32, i32]),
+    "lc_chamfer3d_bwd": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]),
+    "lc_chamfer2d_bwd": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]),
     "lc_bev_grid_supported": (i32, [i32, i32]),
     "lc_bev_occupancy_bits": (i32, [vp, i32, vp, i32, i64, f32, f32, f32, f32, f32, i32, i32, i32, i32, vp, vp, vp]),
     "lc_bev_cell_lists": (i32, [vp, i32, i32, i32, vp, vp, vp]),

@@ -1,25 +1,57 @@
 """Chamfer distance -- mirror of the reference's `lidargen/metrics/modules/chamfer3D/
 dist_chamfer_3D.py` (`chamfer_3DDist`), `modules/chamfer2D/dist_chamfer_2D.py` (`chamfer_2DDist`) and of
-`compute_pairwise_cd` / `compute_pairwise_cd_batch` (`lidargen/metrics/metric_utils.py:415-444`).  Forward only
-(evaluation).  `bev_min_matching` is this project's own: the row minima that compute_mmd averages, on the grid route
-(ops.bev_chamfer_min) or, for a grid that route does not take, on the literal one."""
+`compute_pairwise_cd` / `compute_pairwise_cd_batch` (`lidargen/metrics/metric_utils.py:415-444`).  Both modules are
+differentiable, as in the reference: `chamfer_3DFunction` / `chamfer_2DFunction` are its `torch.autograd.Function`s
+(dist_chamfer_3D.py:28-66), the forward ops.chamfer3d / chamfer2d, the backward ops.chamfer3d_backward /
+chamfer2d_backward -- the reference's gradient terms summed in a fixed order instead of its float atomicAdd, so a loss
+through them has the same gradient bits alone, in any batch and from run to run (csrc/chamfer_bwd.hip).  idx1 / idx2
+are not differentiable, and the backward is differentiable once.  The evaluation callers below pass tensors that need
+no gradient and get the forward's values unchanged.  `bev_min_matching` is this project's own: the row minima that
+compute_mmd averages, on the grid route (ops.bev_chamfer_min) or, for a grid that route does not take, on the literal
+one."""
 from __future__ import annotations
 
 import numpy as np
 import torch
 from torch import nn
+from torch.autograd import Function
+from torch.autograd.function import once_differentiable
 
 from lidarcrafter_amd import ops as K
 
 
+def _chamfer_function(name, fwd, bwd):
+    class _Fn(Function):
+        @staticmethod
+        def forward(ctx, xyz1, xyz2):
+            xyz1, xyz2 = xyz1.contiguous(), xyz2.contiguous()
+            dist1, dist2, idx1, idx2 = fwd(xyz1, xyz2)
+            ctx.save_for_backward(xyz1, xyz2, idx1, idx2)
+            ctx.mark_non_differentiable(idx1, idx2)
+            return dist1, dist2, idx1, idx2
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, graddist1, graddist2, gradidx1, gradidx2):
+            xyz1, xyz2, idx1, idx2 = ctx.saved_tensors
+            return bwd(xyz1, xyz2, graddist1.float().contiguous(), graddist2.float().contiguous(), idx1, idx2)
+
+    _Fn.__name__ = _Fn.__qualname__ = name
+    return _Fn
+
+
+chamfer_3DFunction = _chamfer_function("chamfer_3DFunction", K.chamfer3d, K.chamfer3d_backward)
+chamfer_2DFunction = _chamfer_function("chamfer_2DFunction", K.chamfer2d, K.chamfer2d_backward)
+
+
 class chamfer_3DDist(nn.Module):
     def forward(self, input1, input2):
-        return K.chamfer3d(input1.float(), input2.float())
+        return chamfer_3DFunction.apply(input1.float(), input2.float())
 
 
 class chamfer_2DDist(nn.Module):
     def forward(self, input1, input2):
-        return K.chamfer2d(input1.float(), input2.float())
+        return chamfer_2DFunction.apply(input1.float(), input2.float())
 
 
 def _dev(a):

@@ -2602,6 +2602,52 @@ def chamfer2d(xyz1: torch.Tensor, xyz2: torch.Tensor):
     return d1, d2, i1, i2
 
 
+def _chamfer_backward(dim, xyz1, xyz2, grad_dist1, grad_dist2, idx1, idx2):
+    who = f"chamfer{dim}d_backward"
+    for t, name in ((xyz1, "xyz1"), (xyz2, "xyz2"), (grad_dist1, "grad_dist1"), (grad_dist2, "grad_dist2")):
+        _req(t, name)
+    for t, name in ((idx1, "idx1"), (idx2, "idx2")):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RuntimeError(f"lidarcrafter_amd.ops: `{name}` must be a CUDA(HIP) tensor -- the hot "
+                               "path has no CPU fallback (oracle/ holds the CPU restatement for tests)")
+        if t.dtype != torch.int32:
+            raise TypeError(f"{who}: `{name}` must be int32 (as the forward writes it), got {t.dtype}")
+    if xyz1.dim() != 3 or xyz2.dim() != 3 or xyz1.shape[2] != dim or xyz2.shape[2] != dim or \
+            xyz1.shape[0] != xyz2.shape[0]:
+        raise ValueError(f"{who}: expected [B,N,{dim}] and [B,M,{dim}]")
+    B, N, _ = xyz1.shape
+    M = xyz2.shape[1]
+    if tuple(grad_dist1.shape) != (B, N) or tuple(idx1.shape) != (B, N) or tuple(grad_dist2.shape) != (B, M) or \
+            tuple(idx2.shape) != (B, M):
+        raise ValueError(f"{who}: grad_dist1 / idx1 must be [B,N] = {(B, N)} and grad_dist2 / idx2 [B,M] = {(B, M)}")
+    if B < 1 or N < 1 or M < 1 or B * (N + M) > 2 ** 31 - 2:
+        raise ValueError(f"{who}: B, N, M >= 1 and B * (N + M) < 2^31 - 1, got {(B, N, M)}")
+    xyz1, xyz2, grad_dist1, grad_dist2 = (t.contiguous() for t in (xyz1, xyz2, grad_dist1, grad_dist2))
+    idx1, idx2 = idx1.contiguous(), idx2.contiguous()
+    g1, g2 = torch.empty_like(xyz1), torch.empty_like(xyz2)
+    scratch = torch.empty((lib().lc_chamfer_bwd_scratch_bytes(B, N, M),), device=xyz1.device, dtype=torch.uint8)
+    fn = lib().lc_chamfer3d_bwd if dim == 3 else lib().lc_chamfer2d_bwd
+    check(fn(xyz1.data_ptr(), xyz2.data_ptr(), grad_dist1.data_ptr(), grad_dist2.data_ptr(), idx1.data_ptr(),
+             idx2.data_ptr(), B, N, M, g1.data_ptr(), g2.data_ptr(), scratch.data_ptr(), _stream()), f"lc_chamfer{dim}d_bwd")
+    return g1, g2
+
+
+def chamfer3d_backward(xyz1: torch.Tensor, xyz2: torch.Tensor, grad_dist1: torch.Tensor, grad_dist2: torch.Tensor,
+                       idx1: torch.Tensor, idx2: torch.Tensor):
+    """The gradient of chamfer3d's (dist1, dist2) (dist_chamfer_3D.py:51-66, chamfer3D.cu NmDistanceGradKernel): xyz1 [B,N,3],
+    xyz2 [B,M,3], grad_dist1 [B,N], grad_dist2 [B,M], idx1 / idx2 int32 as chamfer3d returns them -> (grad_xyz1 [B,N,3],
+    grad_xyz2 [B,M,3]).  Row j of grad_xyz1 = 2 g1[j] (x1_j - x2_idx1[j]) plus -(2 g2[k] (x2_k - x1_j)) over the k with
+    idx2[k] == j in ascending k, float32, no atomics: the same bits alone, in any batch and from run to run
+    (csrc/chamfer_bwd.hip gives the order of a long segment).  The table of those k is built on the device by the call."""
+    return _chamfer_backward(3, xyz1, xyz2, grad_dist1, grad_dist2, idx1, idx2)
+
+
+def chamfer2d_backward(xyz1: torch.Tensor, xyz2: torch.Tensor, grad_dist1: torch.Tensor, grad_dist2: torch.Tensor,
+                       idx1: torch.Tensor, idx2: torch.Tensor):
+    """chamfer3d_backward for [B,N,2] / [B,M,2] clouds (chamfer2D.cu NmDistanceGradKernel); any B."""
+    return _chamfer_backward(2, xyz1, xyz2, grad_dist1, grad_dist2, idx1, idx2)
+
+
 class BevGridUnsupported(ValueError):
     """The grid is outside what the distance-transform route takes (lc_bev_grid_supported): callers fall back to the
     literal chamfer_2DDist route."""
