@@ -41,7 +41,8 @@ struct EmdPlan {
 };
 
 // The split of one pair's bid pass for `cnt` bidders: T lanes per point (so 256 / T points per block), `groups` point groups,
-// `nspans` spans of `cps` object chunks.  cnt * nspans <= 256 * max(tgt, groups) <= emd_cap: the triples fit.
+// `nspans` spans of `cps` object chunks.  cnt * nspans <= max(256 * tgt, cnt) <= emd_cap: the triples fit (one span when
+// groups >= tgt; else nspans <= tgt / groups and cnt <= 256 * groups / T).  256 * groups itself may exceed emd_cap at T = 64.
 __device__ __forceinline__ EmdPlan emd_plan(int cnt, int n, int tgt) {
     EmdPlan p;
     p.nch = (n + EMD_CH - 1) / EMD_CH;

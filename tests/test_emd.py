@@ -1,8 +1,11 @@
 """Earth Mover's Distance on the MI355X (csrc/emd.hip, ops.emd_forward, lidargen/metrics/emd.py, eval_utils.evaluate).
-`pytest -m gpu`.  Two pins:
+`pytest -m gpu`.  Three pins:
   * bit for bit against the numpy restatement of the reference's kernels (tests/_emd_oracle.py), on inputs for which the
     restatement counted none of the ties the reference leaves to a race (asserted here, case by case);
-  * independent of the restatement: the auction's eps-optimality against scipy's optimal matching."""
+  * bit for bit against the same restatement under the rule the kernels take where the reference races (rule="device"), on
+    inputs made of ties (a lattice, padded clouds, one repeated object, a cloud against itself), on every route of the bid
+    pass, twice each; on the size ladder n = 1 ... 1025; and on batches of more than 32 pairs;
+  * independent of the restatement: the auction's eps-optimality against scipy's optimal matching, with and without ties."""
 import os
 import sys
 
@@ -93,6 +96,134 @@ def test_eps_optimality_against_scipy():
     opt = O.optimum(a, b)
     print(f"auction {cost:.4f}  optimum {opt:.4f}  gap {cost - opt:.4f}  bound {n * eps:.1f}")
     assert opt - 1e-3 <= cost <= opt + n * eps
+
+
+# ------------------------------------------------------------------------------------------------------------ under ties
+# Bit for bit against the restatement under the DEVICE rule (tests/_emd_oracle.py rule="device": the lowest object index
+# among equal best values, the largest (increment bits, j) pair among an object's bidders), which is defined for every
+# input; test_emd_host.py shows that every choice it makes is one the reference permits, and that these inputs have ties.
+def _forward(a, b, eps=EPS, iters=ITERS, target_blocks=0):
+    """ops.emd_forward on numpy clouds [B, n, 3] -> numpy dist, assignment; range and consistency checked on every run."""
+    from lidarcrafter_amd import ops
+
+    a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
+    dist, asg = ops.emd_forward(torch.from_numpy(a).cuda(), torch.from_numpy(b).cuda(), eps, iters, target_blocks=target_blocks)
+    assert dist.dtype == torch.float32 and asg.dtype == torch.int32 and dist.shape == asg.shape == a.shape[:2]
+    dist, asg = dist.cpu().numpy(), asg.cpu().numpy()
+    n = a.shape[1]
+    assert ((0 <= asg) & (asg < n)).all(), "assignment out of range"
+    d = a - np.take_along_axis(b, asg.astype(np.int64)[..., None], axis=1)
+    want = (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]
+    assert np.array_equal(dist.view(np.uint32), want.view(np.uint32)), "dist is not the distance to the assigned object"
+    return dist, asg
+
+
+def _same(got, want_dist, want_asg, what):
+    dist, asg = got
+    bad = np.flatnonzero(asg != want_asg)
+    assert bad.size == 0, (what, f"{bad.size} assignments differ, first at point {bad[:1]}: {asg[bad[:1]]} for {want_asg[bad[:1]]}")
+    assert np.array_equal(dist.view(np.uint32), want_dist.view(np.uint32)), what
+
+
+def _routes(fam, n, seed, mid, eps=EPS, iters=ITERS):
+    """One pair at target_blocks auto, `mid` and 1, each twice: all six equal to the device-rule restatement, hence to each
+    other and to themselves (the order of the bidder list, which varies from run to run, does not reach the result)."""
+    a, b = O.FAMILIES[fam](n, seed)
+    want = O.case(n, seed, eps, iters, fam, "device")
+    print(f"{fam}({n}, {seed}) eps {eps}: ties (best, window, inc) {(want.ties_best, want.ties_window, want.ties_inc)}, of these in the "
+          f"last pass {(want.last_window, want.last_inc)}; unassigned at the last pass {want.unassigned[-1]}")
+    first = None
+    for tb in (0, mid, 1):
+        print(f"  target_blocks {tb}: (T, spans) visited {sorted(O.splits(want.unassigned, n, 1, tb))}")
+        for rep in range(2):
+            got = _forward(a[None], b[None], eps, iters, tb)
+            got = (got[0][0], got[1][0])
+            _same(got, want.dist, want.assignment, (fam, n, seed, "target_blocks", tb, "run", rep))
+            first = got if first is None else first
+            _same(got, first[0], first[1], (fam, n, seed, "route", tb, "run", rep, "against the first run"))
+    return first
+
+
+@pytest.mark.parametrize("fam,n,seed,mid", O.TIE_CASES, ids=lambda v: str(v))
+def test_ties_bit_exact_on_every_route(fam, n, seed, mid):
+    dist, asg = _routes(fam, n, seed, mid)
+    if fam.startswith("self_pair"):
+        assert not dist.view(np.uint32).any()            # +0.0 exactly
+        want = np.arange(n) if fam == "self_pair" else np.argsort(O.self_pair_perm(n, seed))
+        assert np.array_equal(asg, want)
+
+
+def test_ties_without_an_increment_floor():
+    """eps = 0: every tied increment is +0.0 and the packed word orders by j + 1 alone."""
+    fam, n, seed, eps, iters = O.EPS_ZERO
+    _routes(fam, n, seed, 6, eps, iters)
+
+
+@pytest.mark.parametrize("n", O.LADDER)
+def test_size_ladder(n):
+    """n = 1 (no second best), n < 4, and one below / at / one above the wave, the block and the object chunk."""
+    a, b = O.clouds(n, n)
+    for iters in (ITERS, 1) if n == 1 else (ITERS,):
+        want = O.case(n, n, EPS, iters, "clouds", "device")
+        for tb in (0, 1):
+            got = _forward(a[None], b[None], EPS, iters, tb)
+            _same((got[0][0], got[1][0]), want.dist, want.assignment, (n, "iters", iters, "target_blocks", tb))
+
+
+@pytest.mark.parametrize("B,n,target_blocks", [(33, 96, 0), (33, 600, 0), (40, 96, 0), (40, 600, 0), (40, 600, 64)])
+def test_batch_edges(B, n, target_blocks):
+    """More than 32 pairs: the auto target sits at its floor of 64 blocks per pair and the triple scratch is sized from it.
+    Rows of three families share every launch; each equals the restatement and its own single-pair call (auto target 2048)."""
+    assert O.emd_auto_target(B) == 64
+    rows = O.batch_rows(B, n)
+    cl = [O.FAMILIES[f](m, s) for f, m, s in rows]
+    a, b = np.stack([c[0] for c in cl]), np.stack([c[1] for c in cl])
+    dist, asg = _forward(a, b, target_blocks=target_blocks)
+    for r, (f, m, s) in enumerate(rows):
+        want = O.case(m, s, EPS, ITERS, f, "device")
+        _same((dist[r], asg[r]), want.dist, want.assignment, ("row", r, f, m, s))
+        if target_blocks == 0:
+            one = _forward(a[r:r + 1], b[r:r + 1])
+            _same((dist[r], asg[r]), one[0][0], one[1][0], ("row", r, "against its single-pair call"))
+
+
+@pytest.mark.parametrize("fam,n,seed,eps,iters", O.EPS_OPT, ids=lambda v: str(v))
+def test_eps_optimality_under_ties(fam, n, seed, eps, iters):
+    """Independent of any restatement: a permutation within n * eps (Bertsekas) of scipy's optimal matching.  That everything
+    is assigned before the last iteration is a condition on the inputs, taken from the device-rule restatement."""
+    assert 0 in O.case(n, seed, eps, iters, fam, "device").unassigned[:-1]
+    a, b = O.FAMILIES[fam](n, seed)
+    dist, asg = _forward(a[None], b[None], eps, iters)
+    assert sorted(asg[0].tolist()) == list(range(n))
+    d = a - b[asg[0]]
+    assert np.array_equal(dist[0], (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2])
+    cost = float(np.sqrt(dist[0].astype(np.float64)).sum())
+    opt = O.optimum(a, b)
+    print(f"{fam}({n}, {seed}): auction {cost:.4f}  optimum {opt:.4f}  gap {cost - opt:.4f}  bound {n * eps:.2f}")
+    assert opt - 1e-3 <= cost <= opt + n * eps
+
+
+def test_front_ends_under_ties():
+    from lidargen.metrics.emd import compute_pairwise_emd, compute_pairwise_emd_batch
+
+    x = O.clouds(2048, 21)[0]
+    assert compute_pairwise_emd(x, x) == 0.0
+    for fam in ("padded", "lattice"):
+        a, b = O.FAMILIES[fam](2048, 2048)
+        want = O.case(2048, 2048, EPS, ITERS, fam, "device")
+        assert want.ties_inc > 0
+        ref = float(np.sqrt(want.dist.astype(np.float64)).mean())
+        got = compute_pairwise_emd(a, b)
+        assert abs(got - ref) <= 16 * 2.0 ** -23 * ref, (fam, got, ref)   # the bound of test_compute_pairwise_emd_truncates_and_matches
+    # 34 pairs, 33 of truncated length 1024 (one launch sequence at the floor of the auto target) around one of 2048
+    refs, smps = [], []
+    for r in range(34):
+        fam = ("clouds", "lattice", "padded", "self_pair")[r % 4]
+        a, b = O.FAMILIES[fam](2100 if r == 17 else 1100 + 2 * r, 300 + r)
+        refs.append(a)
+        smps.append(b[:len(b) - 30])      # cut to 2048 (row 17) and to 1024: a padded cloud keeps part of its repeat
+    assert sorted(min(len(r), len(s)) // 1024 for r, s in zip(refs, smps)) == [1] * 33 + [2]
+    assert compute_pairwise_emd_batch(refs, smps) == [compute_pairwise_emd(r, s) for r, s in zip(refs, smps)]
 
 
 def test_call_sequence():
